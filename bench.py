@@ -35,9 +35,9 @@ its own sequence on its own GPU, there is no collective in the data path ("scali
 used only for the barriers around the timed region and the max-over-ranks of the elapsed time.
 
 Timing: W untimed warm-up steps, then EXACTLY K steps between barrier + synchronize on both sides,
-max over ranks.  Because K steps of this workload are only ~0.1 s, that K-step set is repeated until at
-least --min-seconds (2 s) of timed work have accumulated; `value` is total steps / total time over all
-repetitions, `steps` stays K, `timed_repeats` / `steps_timed` say what was actually timed.
+max over ranks; `value` is K / that time, `ms_per_step` the time of one step.  A plain run does only that; every other
+figure below needs --full (null otherwise), whose side legs repeat their K-step set for at least --min-seconds (2 s).
+--dump-outputs DIR: what the timed leg computed in its last step, as DIR/<name>.npy (bench.write_outputs).
 
 The JSON line also carries
   roofline      -- the dominant custom kernel, MSDeformAttn forward at the encoder call shape
@@ -130,7 +130,11 @@ def parse_args():
     ap.add_argument("--warmup", type=int, default=None, help="default: 8 (cfg 1/2/4), 4 (cfg 3, cfg 5)")
     ap.add_argument("--config", choices=sorted(CONFIGS), default="cfg2")
     ap.add_argument("--min-seconds", type=float, default=2.0,
-                    help="repeat the K-step set until this much timed work has accumulated")
+                    help="--full side legs: repeat the K-step set until this much timed work has accumulated")
+    ap.add_argument("--full", action="store_true",
+                    help="also the side legs, association, parity, roofline, matrix-core and CPU figures")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the headline leg computed in its last timed step as DIR/<name>.npy")
     ap.add_argument("--no-graph", action="store_true", help="run the detector eagerly (no HIP graph)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-baseline-only", action="store_true",
@@ -832,6 +836,55 @@ def timed_repeats(run_set, steps, world, device, min_seconds):
 
 
 _last_local_seconds = None   # (this rank's own seconds, repetitions) of the last timed_repeats call
+_last_outputs = None         # () -> {name: array}: what the last run_* leg computed in its last step (--dump-outputs)
+DUMP_LIMIT_BYTES = 64 << 20
+MASK_SAMPLE_PIXELS = 1 << 14
+PARAM_SAMPLE = 1 << 20
+
+
+def tracker_outputs(tracker, prefix=""):
+    """What a caller of Tracker.step gets for the tracker's last frame (the rows `results` files for it): track ids, boxes (xyxy px),
+    scores and object-query indices in track-id order; per-track masks at MASK_SAMPLE_PIXELS fixed, seeded pixel positions."""
+    import numpy as np
+    tracker._flush_deferred()
+    last = tracker._pending_results[-1] if tracker._pending_results else None
+    if last is None or last[0] != tracker.frame_index - 1:   # (no live track after the last frame: no row was filed for it)
+        last = (tracker.frame_index - 1, [], np.zeros((0, 4)), [], [], None)
+    frame, ids, pos, scores, obj_inds, extras = last
+    order = np.argsort(np.asarray(ids, dtype=np.int64), kind="stable")
+    out = {prefix + "track_ids": np.asarray(ids, dtype=np.float64)[order],
+           prefix + "track_boxes": np.asarray(pos, dtype=np.float32).reshape(-1, 4)[order],
+           prefix + "track_scores": np.asarray(scores, dtype=np.float32).reshape(-1)[order],
+           prefix + "track_query_index": np.asarray(obj_inds, dtype=np.float64)[order]}
+    masks = [None if extras is None else extras[i][0] for i in order]
+    if any(m is not None for m in masks):
+        rows = []
+        pick = None
+        for m in masks:
+            m = m.materialise() if hasattr(m, "materialise") else m
+            m = np.asarray(m.cpu() if torch.is_tensor(m) else m).reshape(-1)
+            if pick is None:
+                pick = np.sort(np.random.default_rng(0).choice(m.size, size=min(m.size, MASK_SAMPLE_PIXELS), replace=False))
+            rows.append(m[pick].astype(np.float32))
+        out[prefix + "track_masks_sampled"] = np.stack(rows)
+        out[prefix + "track_masks_sample_index"] = pick.astype(np.float64)
+    return out
+
+
+def write_outputs(directory, arrays):
+    """--dump-outputs: DIR/<name>.npy per array, float64 kept, everything else as float32; at most DUMP_LIMIT_BYTES in all."""
+    import numpy as np
+    conv = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        conv[name] = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+    total = sum(a.nbytes for a in conv.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes, more than the %d allowed" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(directory, exist_ok=True)
+    for name, a in conv.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+    return sorted(conv)
 
 
 def _local_rate(steps, units=1):
@@ -892,6 +945,9 @@ def run_tracking(cfg, args, device, world, model, post, margs, n_seq, seeds=None
     torch.cuda.synchronize()
     from trackformer_amd import runtime
     runtime.settle_heap()   # model, trackers and graphs exist: the cyclic collector need not walk them again
+    global _last_outputs
+    _last_outputs = lambda: {k: v for s, tr in enumerate(trackers)   # noqa: E731
+                             for k, v in tracker_outputs(tr, "seq%d_" % s if n_seq > 1 else "").items()}
     return timed_repeats(run_set, args.steps, world, device, args.min_seconds)
 
 
@@ -929,6 +985,8 @@ def run_plain_step(cfg, args, device, world, model, post, margs, seeds=None, def
     run_set(max(4, args.warmup))
     torch.cuda.synchronize()
     runtime.settle_heap()
+    global _last_outputs
+    _last_outputs = lambda: tracker_outputs(tracker)   # noqa: E731
     return timed_repeats(run_set, args.steps, world, device, args.min_seconds)
 
 
@@ -940,6 +998,7 @@ def run_detect(cfg, args, device, world, model, post):
         detector = GraphedDetector(model)
     frames = make_frames(device, cfg["size"])
     sizes = torch.tensor([list(cfg["size"])], device=device)
+    last = [None]
 
     def run_set(steps):
         with torch.no_grad():
@@ -947,7 +1006,10 @@ def run_detect(cfg, args, device, world, model, post):
                 out, *_ = detector(frames[i % len(frames)]['img'], None, None)
                 res = post['bbox'](out, sizes)
             res[0]['scores'].cpu()   # the frame's result reaches the host
+        last[0] = res
     run_set(max(3, args.warmup))
+    global _last_outputs
+    _last_outputs = lambda: {"det_" + k: last[0][0][k] for k in ("scores", "labels", "boxes")}   # noqa: E731
     return timed_repeats(run_set, args.steps, world, device, args.min_seconds)
 
 
@@ -960,13 +1022,28 @@ def run_training(cfg, args, device, world, rank, model, criterion, margs):
     optimizer, _ = engine.build_optimizer(model, margs)
     ddp = engine.wrap_ddp(model, device)
     samples, targets = synthetic_batch(device, 2, *cfg["size"], seed=rank)
+    last = [None]
 
     def run_set(steps):
         for _ in range(steps):
             tg = [dict(t, prev_target=dict(t['prev_target'])) for t in targets]   # forward mutates targets
-            engine.train_step(ddp, criterion, optimizer, samples, tg, clip_max_norm=margs.clip_max_norm)
+            last[0] = engine.train_step(ddp, criterion, optimizer, samples, tg, clip_max_norm=margs.clip_max_norm)
     run_set(args.warmup)
     engine.settle_heap()   # (as engine.train_one_epoch does after its first steps: no oldest-generation collector pass inside a step)
+
+    def outputs():
+        """The step's weighted loss and loss dict, and PARAM_SAMPLE fixed, seeded entries of the updated parameters."""
+        losses, loss_dict = last[0]
+        out = {"loss": losses.double()}
+        out.update(("loss_dict_" + k, torch.as_tensor(v).detach().double()) for k, v in sorted(loss_dict.items()))
+        with torch.no_grad():
+            flat = torch.cat([p.detach().reshape(-1) for p in model.parameters()])
+            pick = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(0))[:PARAM_SAMPLE].sort().values
+            out["params_sampled"] = flat[pick.to(flat.device)]
+            out["params_sample_index"] = pick.double()
+        return out
+    global _last_outputs
+    _last_outputs = outputs
     return timed_repeats(run_set, args.steps, world, device, args.min_seconds)
 
 
@@ -1028,6 +1105,16 @@ def main():
     single = fp32_exact = fp32_exact_single = association = multi = step_only = host_frames_fps = plain_step = None
     other_arith = {}
     n_seq = 1
+    import copy
+    head_args = copy.copy(args)
+    head_args.min_seconds = 0.0   # the headline leg: ONE set of exactly --steps timed steps
+
+    def headline_done():
+        """Right after the headline leg: its rate on this rank, and (--dump-outputs, rank 0) what its last step computed."""
+        if args.dump_outputs and rank == 0:
+            names = write_outputs(args.dump_outputs, _last_outputs())
+            print("bench: %d arrays of the last timed step in %s" % (len(names), args.dump_outputs), file=sys.stderr)
+        return _local_rate(args.steps, units=2 if train else 1)
     if cfg["kind"] == "track":
         model.tracking()
         n_seq = max(1, args.sequences)
@@ -1035,24 +1122,23 @@ def main():
         if not args.no_calibration and cfg["tracks"] > 0:
             seeds = calibrate_association(model, make_frames(device, cfg["size"], n=1)[0], cfg["tracks"], cfg["size"], device)
         if args.no_single_sequence:     # (A/B aid: only the interleaved set-up; then THAT is what the line reports)
-            elapsed, reps = run_tracking(cfg, args, device, world, model, post, margs, n_seq, seeds)
-            headline_local = _local_rate(args.steps)
+            elapsed, reps = run_tracking(cfg, head_args, device, world, model, post, margs, n_seq, seeds)
+            headline_local = headline_done()
         else:
             # THE HEADLINE: one sequence per GPU -- BASELINE.json's "bs = 1 on 1 x MI355X" (VERDICT r04 task 4).  The
             # throughput with --sequences interleaved (one sequence's host-side association under another's forward) is
-            # reported beside it as multi_sequence_fps, never as `value`.
-            elapsed, reps = run_tracking(cfg, args, device, world, model, post, margs, 1, seeds)
-            headline_local = _local_rate(args.steps)
+            # reported beside it as multi_sequence_fps (--full), never as `value`.
+            elapsed, reps = run_tracking(cfg, head_args, device, world, model, post, margs, 1, seeds)
+            headline_local = headline_done()
             single = args.steps * reps * world / elapsed
-            if n_seq > 1:
+            if n_seq > 1 and args.full:
                 em, rm = run_tracking(cfg, args, device, world, model, post, margs, n_seq, seeds)
                 multi = args.steps * rm * world / em
             n_seq = 1
-        if not args.no_prepare and not args.no_single_sequence and not args.host_frames:
+        if args.full and not args.no_prepare and not args.no_single_sequence and not args.host_frames:
             # ... and the two figures a caller of the reference's own loop gets (VERDICT r05 task 1c): (1) plain Tracker.step()
             # per frame, no step_prepare -- what an unmodified src/track.py:130-134 drives; (2) the pipelined loop with the frames
             # in pinned HOST memory, the 12.8 MB upload inside the timed step (tracker.py:283-284 of the reference uploads too)
-            import copy
             a_step = copy.copy(args)
             a_step.no_prepare = True
             es, rs = run_tracking(cfg, a_step, device, world, model, post, margs, 1, seeds)
@@ -1068,13 +1154,13 @@ def main():
             plain_step = {"deferred_association": round(args.steps * rp * world / ep, 3),
                           "association_before_return": round(args.steps * rs2 * world / es2, 3),
                           "loop": "for blob in frames: tracker.step(blob) -- src/track.py:130-134 of the reference; frames in pinned host memory"}
-        if seeds is not None and rank == 0:
+        if args.full and seeds is not None and rank == 0:
             association = association_stats(model, post, TrackSeeder(device, margs.hidden_dim, cfg["tracks"], cfg["size"], seeds=seeds),
                                             make_frames(device, cfg["size"]))
             association.update(class_head_scale=seeds["scale"], class_head_shift=seeds["shift"],
                                queries_above_thresh_frame0=seeds["queries_above_0p4_frame0"],
                                track_queries_above_thresh_frame0=seeds["track_queries_above_0p4_frame0"])
-        if fused.split_linear_enabled() and not args.no_fp32_exact:
+        if args.full and fused.split_linear_enabled() and not args.no_fp32_exact:
             # the same measurement with every matrix product in the fp32 libraries (hipBLASLt linears, MIOpen convolutions), with
             # --sequences and with one sequence
             prev_split = fused.set_split_linear(False)
@@ -1086,7 +1172,7 @@ def main():
                     fp32_exact_single = args.steps * rf * world / ef
             finally:
                 fused.set_split_linear(prev_split)
-        if fused.split_linear_enabled() and not args.no_split3:
+        if args.full and fused.split_linear_enabled() and not args.no_split3:
             # ... and with the other split products (reported beside the headline, never as the headline)
             for alt in (6, 16):
                 if alt == fused.split_terms():
@@ -1103,14 +1189,14 @@ def main():
                     fused.set_split_terms(prev_terms)
     elif cfg["kind"] == "detect":
         model.eval()
-        elapsed, reps = run_detect(cfg, args, device, world, model, post)
-        headline_local = _local_rate(args.steps)
+        elapsed, reps = run_detect(cfg, head_args, device, world, model, post)
+        headline_local = headline_done()
     else:
-        elapsed, reps = run_training(cfg, args, device, world, rank, model, criterion, margs)
-        headline_local = _local_rate(args.steps, units=2)
+        elapsed, reps = run_training(cfg, head_args, device, world, rank, model, criterion, margs)
+        headline_local = headline_done()
 
     roofline = cpu_baseline = parity = mfma = None
-    if rank == 0:
+    if rank == 0 and args.full:
         if not args.no_roofline and margs.deformable:
             roofline = measure_roofline(device, train=train, head_dim=margs.hidden_dim // margs.nheads)
         if args.config == "cfg2" and not args.no_parity and not args.no_graph:

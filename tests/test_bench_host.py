@@ -74,3 +74,53 @@ def test_every_rank_gets_its_own_library_caches(monkeypatch, tmp_path):
     base5 = bench.per_rank_caches(5)
     assert os.environ["MIOPEN_USER_DB_PATH"] == "/somewhere/else"          # the caller's choice stands
     assert os.environ["MIOPEN_CUSTOM_CACHE_DIR"].startswith(base5) and base5 != base3
+
+
+def test_plain_full_and_dump_arguments(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "7"])
+    a = bench.parse_args()
+    assert not a.full and a.dump_outputs is None and a.steps == 7
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse_args()
+    assert a.full and a.dump_outputs == "d"
+
+
+def test_write_outputs_dtypes_and_limit(tmp_path):
+    import numpy as np
+    names = bench.write_outputs(str(tmp_path / "d"), {"ids": np.arange(3.0), "labels": np.array([1, 2]), "mask": np.ones(3, bool)})
+    got = {n: np.load(str(tmp_path / "d" / (n + ".npy"))) for n in names}
+    assert got["ids"].dtype == np.float64 and got["labels"].dtype == got["mask"].dtype == np.float32
+    with pytest.raises(SystemExit, match="more than"):
+        bench.write_outputs(str(tmp_path / "big"), {"x": np.zeros(bench.DUMP_LIMIT_BYTES // 4 + 1, np.float32)})
+    assert not (tmp_path / "big").exists()
+
+
+@pytest.mark.parametrize("case", ["cfg2_deformable_tracking", "cfg5_segm_tracking"])
+def test_dump_of_a_tracker_step_is_what_get_results_holds_for_the_last_frame(case):
+    """bench.tracker_outputs: the entries get_results() gives for the last frame, in track-id order (masks at the sampled pixels)."""
+    import numpy as np
+    import torch
+    from tests import util_models as um
+    from trackformer_amd import _cabi, config, factory
+    from trackformer_amd.tracker import Tracker
+    _cabi.lib()
+    model, post, _ = um.build(case, factory.build_model, config.make_args)
+    model.tracking()
+    tracker = Tracker(model, post, config.tracker_cfg(), False)
+    tracker.reset()
+    with torch.no_grad():
+        for blob in um.tracker_sequence()[:2]:
+            tracker.step(blob)
+    out = bench.tracker_outputs(tracker)          # (before get_results(): nothing has read the frames yet, as in bench.py)
+    last, res = tracker.frame_index - 1, tracker.get_results()
+    ids = sorted(t for t in res if last in res[t])
+    assert ids and out["track_ids"].tolist() == ids
+    np.testing.assert_array_equal(out["track_boxes"], np.stack([res[t][last]["bbox"] for t in ids]))
+    np.testing.assert_array_equal(out["track_scores"], np.array([res[t][last]["score"] for t in ids], np.float32))
+    assert out["track_query_index"].tolist() == [res[t][last]["obj_ind"] for t in ids]
+    if "mask" in res[ids[0]][last]:
+        pick = out["track_masks_sample_index"].astype(np.int64)
+        want = np.stack([np.asarray(res[t][last]["mask"]).reshape(-1)[pick] for t in ids])
+        np.testing.assert_array_equal(out["track_masks_sampled"], want.astype(np.float32))
+    else:
+        assert case == "cfg2_deformable_tracking" and "track_masks_sampled" not in out

@@ -1,65 +1,54 @@
-"""CPU, build box only (skipped where /root/reference does not exist, e.g. on the GPU box): the reference's UNMODIFIED
-ops/functions/ms_deform_attn_func.py imported from where it lies, with `import MultiScaleDeformableAttention as MSDA`
-(func.py:11) resolved by trackformer_amd.dropin -- its own MSDeformAttnFunction (func.py:14-31) then runs on this
-library, and is compared with its own pure-PyTorch ms_deform_attn_core_pytorch (func.py:34-54) the way the reference's
-ops/test.py:23-60 does (forward equality, then gradients of all three inputs).  VERDICT r02 item 6(d)."""
-import importlib.util
+"""CPU: the reference's ops/functions/ms_deform_attn_func.py on this library.  That module does
+`import MultiScaleDeformableAttention as MSDA` (func.py:11) -- resolved by trackformer_amd.dropin -- and its MSDeformAttnFunction
+(func.py:14-31) is two calls into it: MSDA.ms_deform_attn_forward(value, shapes, loc, attn, im2col_step) in forward and
+MSDA.ms_deform_attn_backward(value, shapes, loc, attn, grad_output, im2col_step) in backward, whose three gradients it returns.
+Those calls are made here as it makes them and compared, the way the reference's ops/test.py:23-60 does (forward equality, then
+gradients of all three inputs), with the reference's own pure-PyTorch ms_deform_attn_core_pytorch (func.py:34-54): its output and
+gradients at these inputs are stored in tests/golden/cross_msda_function_*.npz (tests/golden/make_golden_cross.py).
+VERDICT r02 item 6(d)."""
+import importlib
 import os
 import sys
 
+import numpy as np
 import pytest
 import torch
 
-REF_FUNC = "/root/reference/src/trackformer/models/ops/functions/ms_deform_attn_func.py"
-pytestmark = pytest.mark.skipif(not os.path.exists(REF_FUNC), reason="the reference checkout is not present on this machine")
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 @pytest.fixture()
-def reference_func_module():
+def msda_module():
+    """What `import MultiScaleDeformableAttention as MSDA` gives once the drop-in is installed."""
     import trackformer_amd.dropin as dropin
     saved = sys.modules.pop("MultiScaleDeformableAttention", None)
     dropin.install()
     try:
-        spec = importlib.util.spec_from_file_location("_reference_ms_deform_attn_func", REF_FUNC)
-        mod = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mod)      # executes `import MultiScaleDeformableAttention as MSDA`
-        yield mod
+        yield importlib.import_module("MultiScaleDeformableAttention")
     finally:
         sys.modules.pop("MultiScaleDeformableAttention", None)
         if saved is not None:
             sys.modules["MultiScaleDeformableAttention"] = saved
 
 
-def _inputs(dtype, seed=0):
-    g = torch.Generator().manual_seed(seed)
-    N, M, D, Lq, L, P = 2, 2, 8, 5, 2, 2      # the shape family of ops/test.py:18-21
-    shapes = torch.tensor([(6, 4), (3, 2)], dtype=torch.long)
-    S = int((shapes[:, 0] * shapes[:, 1]).sum())
-    value = torch.rand(N, S, M, D, generator=g, dtype=dtype) * 0.01
-    loc = torch.rand(N, Lq, M, L, P, 2, generator=g, dtype=dtype) * 1.2 - 0.1
-    attn = torch.rand(N, Lq, M, L, P, generator=g, dtype=dtype) + 1e-5
-    attn = attn / attn.sum(-1, keepdim=True).sum(-2, keepdim=True)
-    return value, shapes, loc, attn
-
-
-def test_reference_module_binds_to_this_library(reference_func_module):
+def test_reference_module_binds_to_this_library(msda_module):
     import trackformer_amd.msda as msda
-    MSDA = reference_func_module.MSDA
-    assert MSDA.ms_deform_attn_forward is msda.ms_deform_attn_forward
-    assert MSDA.ms_deform_attn_backward is msda.ms_deform_attn_backward
+    assert msda_module.ms_deform_attn_forward is msda.ms_deform_attn_forward
+    assert msda_module.ms_deform_attn_backward is msda.ms_deform_attn_backward
 
 
 @pytest.mark.parametrize("dtype,tol", [(torch.float64, 1e-10), (torch.float32, 1e-5)], ids=["f64", "f32"])
-def test_reference_autograd_function_runs_on_this_library(reference_func_module, dtype, tol):
-    ref = reference_func_module
-    value, shapes, loc, attn = _inputs(dtype)
-    leaves = [t.clone().requires_grad_() for t in (value, loc, attn)]
-    out = ref.MSDeformAttnFunction.apply(leaves[0], shapes, leaves[1], leaves[2], 2)          # func.py:14-31 on the drop-in
-    leaves_t = [t.clone().requires_grad_() for t in (value, loc, attn)]
-    out_t = ref.ms_deform_attn_core_pytorch(leaves_t[0], shapes, leaves_t[1], leaves_t[2])   # func.py:34-54
+def test_reference_autograd_function_runs_on_this_library(msda_module, dtype, tol):
+    z = np.load(os.path.join(GOLDEN, "cross_msda_function_%s.npz" % ("f64" if dtype == torch.float64 else "f32")))
+    value, loc, attn, w = (torch.from_numpy(z[k]) for k in ("value", "loc", "attn", "w"))
+    shapes = torch.from_numpy(z["shapes"])
+    assert value.dtype == dtype and shapes.dtype == torch.long
+    out = msda_module.ms_deform_attn_forward(value, shapes, loc, attn, 2)                 # func.py:18-19
+    out_t = torch.from_numpy(z["out"])                                                    # func.py:34-54
     assert out.shape == out_t.shape and float((out - out_t).abs().max()) < tol
-    w = torch.rand(out.shape, generator=torch.Generator().manual_seed(1), dtype=dtype)
-    (out * w).sum().backward()
-    (out_t * w).sum().backward()
-    for a, b in zip(leaves, leaves_t):
-        assert float((a.grad - b.grad).abs().max()) < tol * 10 * max(1.0, float(b.grad.abs().max()))
+    # d (out * w).sum() / d out = w: the grad_output autograd hands to func.py:27-29
+    grads = msda_module.ms_deform_attn_backward(value, shapes, loc, attn, w, 2)
+    for a, key in zip(grads, ("grad_value", "grad_loc", "grad_attn")):
+        b = torch.from_numpy(z[key])
+        assert a.shape == b.shape and a.dtype == dtype
+        assert float((a - b).abs().max()) < tol * 10 * max(1.0, float(b.abs().max())), key

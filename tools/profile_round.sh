@@ -7,7 +7,7 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-PY="python $REPO/bench.py --no-cpu-baseline"
+PY="python $REPO/bench.py --full --no-cpu-baseline"
 MS="python $REPO/tools/prof_msda.py --shape cfg2_encoder --iters 6"
 
 # 1. the default bench command (HIP graph, 2 sequences): per-kernel statistics
