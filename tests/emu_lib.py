@@ -209,7 +209,7 @@ def f16_split(w):
     w = w.astype(np.float32)
     amax = np.abs(w).max(axis=1)
     _, e = np.frexp(amax)                       # amax = m 2^e, m in [0.5, 1)
-    t = np.ldexp(np.float32(1), np.clip(14 - e, -100, 100)).astype(np.float32)
+    t = np.ldexp(np.float32(1), np.clip(14 - e, -100, 126)).astype(np.float32)
     t = np.where((amax > 0) & (amax < 3.0e38), t, np.float32(1)).astype(np.float32)
     ws = (w * t[:, None]).astype(np.float32)
     hi = ws.astype(np.float16)

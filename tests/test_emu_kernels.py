@@ -1193,3 +1193,92 @@ def test_relu_epilogues_propagate_nan_instead_of_zeroing_it(terms):
         assert np.isnan(out[1, 3]) and np.isfinite(np.delete(out.ravel(), 64 + 3)).all()
     finally:
         emu_lib.set_terms(prev_terms)
+
+
+# ---- the magnitude profiles of tests/util_split_numerics.py on the emulated matrix cores (twins of tests/test_split_product_gpu.py) --------
+def _twin_ln(pre, S, floor, nan, g, be, y):
+    from tests import util_split_numerics as U
+    import torch
+    ref, Sn, fn, nan_n = U.layernorm_reference(pre, S, floor, torch.from_numpy(g), torch.from_numpy(be), 1e-5, nan)
+    return U.check(torch.from_numpy(y), ref, Sn, fn, nan_n)
+
+
+@pytest.mark.parametrize("profile", ["unit", "small_x", "large_x", "row_spread", "channel_spread", "edge_values", "nonfinite"])
+def test_fp16_product_profiles_linear_res_ln_and_linear_add(profile):
+    """tf_linear_res_ln_f32 (norm-aware bound) and tf_linear_split_add_f32 (against float64 of x + pos) under the fp16 product in every
+    magnitude profile, with the float64 yardstick of the GPU tests."""
+    import torch
+    from tests import util_split_numerics as U
+    M, D = 70, 256
+    x, w, b, r = U.linear_operands(profile, M, D, D, seed=21, residual=True)
+    g, be = (1 + 0.1 * torch.randn(D, generator=torch.Generator().manual_seed(1))), 0.1 * torch.randn(D, generator=torch.Generator().manual_seed(2))
+    prev = emu_lib.set_terms(16)
+    try:
+        y = emu_lib.linear_res_ln(x.numpy(), w.numpy(), b.numpy(), r.numpy(), ln=(g.numpy(), be.numpy()))
+        pos = U.linear_operands("unit" if profile in ("nonfinite", "large_x") else profile, M, D, 96, seed=22)[0]
+        w2, b2 = w[:96].contiguous(), b[:96].contiguous()
+        ya = emu_lib.linear_split_add(x.numpy(), pos.numpy(), w2.numpy(), b2.numpy())
+    finally:
+        emu_lib.set_terms(prev)
+    pre, S, floor, nan = U.linear_reference(x, w, b, r, terms=16)
+    _twin_ln(pre, S, floor, nan, g.numpy(), be.numpy(), y)
+    ref, _, _, nan = U.linear_reference(x.double() + pos.double(), w2, b2, terms=16)
+    S = U.linear_reference(x.abs() + pos.abs(), w2, b2, terms=16)[1]
+    U.check(torch.from_numpy(ya), ref, S, U.small_floor(x + pos, w2, 16), nan, fp32=U.linear_fp32(x + pos, w2, b2))
+
+
+@pytest.mark.parametrize("profile", ["unit", "small_x", "large_x", "row_spread", "channel_spread", "edge_values", "nonfinite"])
+def test_fp16_product_profiles_fused_ffn(profile):
+    """tf_ffn_fused_f32 (hidden 288 in chunks of 96: F = 160) with the LayerNorm epilogue: float64 of the whole block, the hidden layer
+    rounded to fp32 and its bound carried through |w2|."""
+    import torch
+    from tests import util_split_numerics as U
+    M, D, Fd = 40, 288, 160
+    x, w1, b1, _ = U.linear_operands(profile, M, D, Fd, seed=23)
+    _, w2, b2, _ = U.linear_operands("unit" if profile in ("large_x", "small_x", "row_spread", "nonfinite") else profile, 4, Fd, D, seed=24)
+    g, be = (1 + 0.1 * torch.randn(D, generator=torch.Generator().manual_seed(1))), 0.1 * torch.randn(D, generator=torch.Generator().manual_seed(2))
+    prev = emu_lib.set_terms(16)
+    opts = emu_lib.set_options(ffn_ti=1)
+    try:
+        y = emu_lib.ffn_fused(x.numpy(), w1.numpy(), b1.numpy(), w2.numpy(), b2.numpy(), residual=x.numpy(), ln=(g.numpy(), be.numpy()))
+    finally:
+        emu_lib.set_options(**opts)
+        emu_lib.set_terms(prev)
+    h, S1, floor1, nan1 = U.linear_reference(x, w1, b1, relu=True, terms=16)
+    hmax = torch.where(nan1, torch.zeros_like(h), h.abs()).amax(1)
+    keep = ~((hmax > 0.98 * U.F16_ACTIVATION_LIMIT) & (hmax < 1.02 * U.F16_ACTIVATION_LIMIT))
+    e1 = torch.where(nan1, torch.zeros_like(h), floor1 + U.BOUND * S1)
+    pre, S2, floor2, nan2 = U.linear_reference(torch.where(nan1, h, h.float().double()), w2, b2, x, terms=16)
+    floor = floor2 + e1 @ w2.double().abs().t()
+    nan = nan2 | nan1.any(1, keepdim=True)
+    _twin_ln(pre[keep], S2[keep], floor[keep], nan[keep], g.numpy(), be.numpy(), y[keep.numpy()])
+
+
+@pytest.mark.parametrize("profile", ["unit", "small_x", "large_x", "row_spread", "channel_spread", "edge_values", "nonfinite"])
+def test_fp16_product_profiles_convolutions(profile):
+    """tf_conv_packed_f32 -- stream form (3 x 3 stride 2, 1 x 1), halo form, split-K pieces that do not divide K -- and
+    tf_stem_conv7x7_f32 (+ shift + ReLU) under the fp16 product in every magnitude profile."""
+    import torch
+    from tests import util_split_numerics as U
+    prev = emu_lib.set_terms(16)
+    try:
+        for (n, h, w, cin, cout, ks, stride, ksplit, halo) in [(1, 7, 5, 64, 64, 3, 2, 1, 0), (1, 5, 4, 64, 96, 1, 1, 1, 0),
+                                                                (1, 6, 5, 64, 64, 3, 1, 1, 1), (1, 5, 3, 64, 64, 3, 1, 5, 0)]:
+            x, wt, b = U.conv_operands(profile, n, cin, h, w, cout, ks, seed=h * w + cin)
+            x_nhwc = x.permute(0, 2, 3, 1).contiguous().numpy()
+            opts = emu_lib.set_options(conv_halo=halo)
+            try:
+                y = emu_lib.conv_packed(x_nhwc, wt.permute(0, 2, 3, 1).contiguous().numpy(), b.numpy(), relu=True, stride=stride, ksplit=ksplit)
+            finally:
+                emu_lib.set_options(**opts)
+            pad = 1 if ks == 3 else 0
+            ref, S, floor, nan = U.conv_reference(x, wt, b, stride, pad, True, 16)
+            U.check(torch.from_numpy(y).reshape(-1, cout), ref, S, floor, nan, fp32=U.conv_fp32(x, wt, b, stride, pad, True))
+        x, wt, b = U.conv_operands(profile, 1, 3, 9, 11, 64, 7, seed=5)
+        x = x.contiguous()
+        for bias, relu in ((None, False), (b, True)):
+            y = emu_lib.stem_conv(x.numpy(), wt.numpy(), None if bias is None else bias.numpy(), relu=relu)
+            ref, S, floor, nan = U.conv_reference(x, wt, bias, 2, 3, relu, 16)
+            U.check(torch.from_numpy(y).reshape(-1, 64), ref, S, floor, nan, fp32=U.conv_fp32(x, wt, bias, 2, 3, relu))
+    finally:
+        emu_lib.set_terms(prev)

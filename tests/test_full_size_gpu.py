@@ -602,6 +602,10 @@ def test_conv3x3_split_k(dev, shape, cout, stride, ksplit):
     ref = torch.relu(torch.nn.functional.conv2d(x, w, b, stride=stride, padding=1)).permute(0, 2, 3, 1)
     assert torch.equal(outs[0], outs[1])
     assert float((outs[0] - ref).abs().max()) < 1e-3 * float(ref.abs().max())
+    # and against float64 with the split product's bound (tests/util_split_numerics.py)
+    from tests import util_split_numerics as U
+    r64, S, floor, nan = U.conv_reference(x, w, b, stride, 1, True, fused.split_terms())
+    U.check(outs[0].reshape(-1, cout), r64, S, floor, nan, fp32=U.conv_fp32(x, w, b, stride, 1, True), k=9 * cin)
 
 
 @pytest.mark.parametrize("shape,cout,stride", [((1, 1024, 50, 84), 256, 1), ((1, 2048, 25, 42), 512, 1), ((1, 2048, 25, 42), 256, 1),
@@ -627,6 +631,13 @@ def test_conv1x1_split_k(dev, shape, cout, stride):
     scale = float(ref.abs().max())
     assert torch.equal(y1, y2)
     assert float((y1 - y0).abs().max()) < 1e-5 * scale and float((y1 - ref).abs().max()) < 1e-3 * scale
+    # and both, cut and uncut, against float64 with the split product's bound (tests/util_split_numerics.py)
+    from tests import util_split_numerics as U
+    w4 = w[:, :, None, None]
+    r64, S, floor, nan = U.conv_reference(x, w4, b, stride, 0, True, fused.split_terms())
+    fp32 = U.conv_fp32(x, w4, b, stride, 0, True)
+    for y in (y1, y0):
+        U.check(y.permute(0, 2, 3, 1).reshape(-1, cout), r64, S, floor, nan, fp32=fp32, k=shape[1])
     if cut >= 3:
         assert fused.conv1x1_wants_split_k(m, shape[1], cout)
     else:

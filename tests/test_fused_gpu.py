@@ -192,6 +192,16 @@ def test_fused_ffn_block(rows, ti, d, monkeypatch):
     assert torch.equal(got, ref)
     assert torch.allclose(got, exact, atol=2e-4, rtol=1e-4)
     assert torch.allclose(got_ln, norm(ref), atol=1e-5, rtol=1e-5)
+    # and against float64 of the whole block (tests/util_split_numerics.py): the hidden layer's bound carried through |w2|
+    from tests import util_split_numerics as U
+    terms = fused.split_terms()
+    x2 = x.reshape(rows, d)
+    h, S1, floor1, _ = U.linear_reference(x2, l1.weight.detach(), l1.bias.detach(), relu=True, terms=terms)
+    pre, S2, floor2, nan = U.linear_reference(h.float().double(), l2.weight.detach(), l2.bias.detach(), x2, terms=terms)
+    floor = floor2 + (floor1 + U.BOUND * S1) @ l2.weight.detach().double().abs().t()
+    U.check(got.reshape(rows, d), pre, S2, floor, nan)
+    ref_ln, S_ln, floor_ln, nan_ln = U.layernorm_reference(pre, S2, floor, norm.weight.detach(), norm.bias.detach(), norm.eps, nan)
+    U.check(got_ln.reshape(rows, d), ref_ln, S_ln, floor_ln, nan_ln)
 
 
 @pytest.mark.parametrize("rows,ti,d", [(22223, 0, 256), (22223, 3, 256), (400, 0, 256), (97, 2, 256), (22223, 0, 288), (800, 0, 288)])
@@ -255,6 +265,14 @@ def test_stem_convolution_split(shape):
     scale = float(ref.abs().max())
     assert float((got - ref).abs().max()) < 1e-3 * scale
     assert float((got_b - torch.relu(ref + b.view(1, -1, 1, 1))).abs().max()) < 1e-3 * scale
+    # and against float64 with the split product's bound (tests/util_split_numerics.py), the full frame on sampled pixels
+    from tests import util_split_numerics as U
+    m = got.shape[0] * got.shape[2] * got.shape[3]
+    rows = torch.randperm(m, generator=torch.Generator().manual_seed(1))[:8192] if m > 20000 else None
+    for y, bias, relu in ((got, None, False), (got_b, b, True)):
+        r64, S, floor, nan = U.conv_reference(x, w, bias, 2, 3, relu, fused.split_terms(), rows=rows)
+        y2 = y.permute(0, 2, 3, 1).reshape(m, 64)
+        U.check(y2 if rows is None else y2[rows.to(dev)], r64, S, floor, nan, fp32=U.conv_fp32(x, w, bias, 2, 3, relu, rows=rows))
 
 
 def test_fp16_product_range_contract_is_loud_and_has_a_way_out(dev):

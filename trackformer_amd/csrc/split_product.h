@@ -46,6 +46,10 @@ typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;   // 4 pieces of
 //     output row is NaN, loudly, instead of silently saturated.
 // Measured against float64 on random operands (tools/experiments/f16_split.py): max |err| / sum |x||w| = 3.7e-8 for the
 // representation alone (fp32 rounding of the SUM, which the reference's sgemm has as well: 2.4e-7), six-term bf16 3.3e-9.
+// On the chip (MI355X, tests/test_split_product_gpu.py, every kernel that includes this header): v_mfma_f32_32x32x16_f16 and
+// v_cvt_f16_f32 keep fp16 SUBNORMAL operands under the kernels' default float mode -- activations x 1e-4 (hi piece subnormal) come
+// out at max (|err| - 2^-31 sum_{|x| < 2^-10} |w|) / sum |x||w| = 1.1e-7, unit operands 2.2e-7, rows spread by 1e4 5.5e-7 (six
+// terms: 2.4e-7 / 3.0e-7 / 6.7e-7); torch's fp32 sgemm of the same operands reaches the same order (up to 6.4e-7 at K = 2592).
 // Terms are issued smallest first.
 template <int SP> struct Split;
 // NA / NB: pieces of an activation / of a weight as STORED (LDS, packed image, piece tensors); NBX: weight operands of the terms (B
@@ -125,13 +129,17 @@ __device__ __forceinline__ void expand_weight(const u32x4 (&w)[Split<SP>::NB], u
     }
 }
 
-// the power of two that puts `amax` (the largest |w| of an output channel) into [2^13, 2^14); 1 for an all-zero / non-finite channel
+// the power of two that puts `amax` (the largest |w| of an output channel) into [2^13, 2^14); 1 for an all-zero / non-finite channel.
+// Capped at 2^126 (t_n and r_n = 2^4 / t_n both normal fp32): a channel whose largest |w| lies below 2^-112 -- fp32 subnormals
+// included, whose exponent field reads as 2^-127 here -- is scaled by 2^126, which leaves its hi piece normal and its pieces an
+// absolute error below 2^-150 |x| per product in the channel's own units (fp32's own spacing there is 2^-149).  (A cap of 2^100, as
+// before, left a channel of fp32 subnormals below the fp16 subnormals: all of its products were zero.)
 __device__ __forceinline__ float weight_scale_for(float amax)
 {
     if (!(amax > 0.f) || !(amax < 3.0e38f)) return 1.f;
     const int e = (int)((__builtin_bit_cast(unsigned, amax) >> 23) & 0xffu) - 127;   // floor(log2 amax) for normal numbers
     int s = 13 - e;
-    s = s < -100 ? -100 : (s > 100 ? 100 : s);
+    s = s < -100 ? -100 : (s > 126 ? 126 : s);
     return __builtin_bit_cast(float, (unsigned)(s + 127) << 23);
 }
 

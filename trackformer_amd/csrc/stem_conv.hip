@@ -146,6 +146,9 @@ stem_conv7x7_kernel(const float *__restrict__ X, const u32x4 *__restrict__ Wp, c
                 xv[2 * e2] = t2.x;
                 xv[2 * e2 + 1] = t2.y;
             }
+            // kx = 7 pads a kernel row to 8 taps: its weight is zero, but it reads the pixel right of the 7 x 7 window, and a NaN or an
+            // over-limit value there (0 . NaN = NaN) would reach an output whose window does not hold it -- the tap reads zero instead
+            xv[7] = 0.f;
             if (2 * q + 1 > kLast) {   // the last step's upper half is padding: its weights are zero, keep the data finite
 #pragma unroll
                 for (int e = 0; e < 8; ++e) xv[e] = half ? 0.f : xv[e];

@@ -251,7 +251,7 @@ def _split_weight(weight):
             amax = w.abs().amax(dim=1)
             _, e = torch.frexp(amax)                                   # amax = m 2^e with m in [0.5, 1): floor(log2 amax) = e - 1
             # 2^(14 - e) from its exponent bits (torch.ldexp goes through pow(), which is not exact on every device)
-            t = ((torch.clamp(14 - e, -100, 100).to(torch.int32) + 127) << 23).view(torch.float32)
+            t = ((torch.clamp(14 - e, -100, 126).to(torch.int32) + 127) << 23).view(torch.float32)   # (cap: split_product.h)
             t = torch.where((amax > 0) & (amax < 3.0e38), t, torch.ones_like(t))
             ws = w * t[:, None]                                        # exact: powers of two
             hi = ws.to(torch.float16)
