@@ -96,6 +96,8 @@ def lib():
     L.tf_conv_packed_f32.argtypes = [vp, vp, vp, vp, vp, vp] + [ci] * 10 + [vp]
     L.tf_mha_core_f32.restype = ci
     L.tf_mha_core_f32.argtypes = [vp, vp, vp, vp, vp] + [ci] * 9 + [ctypes.c_float, vp]
+    L.tf_msda_last_kernel.restype = ctypes.c_char_p
+    L.tf_msda_last_kernel.argtypes = []
     L.hipemu_get_stats.restype = None
     L.hipemu_get_stats.argtypes = [vp]
     L.hipemu_reset_stats.restype = None
@@ -116,6 +118,11 @@ def set_options(**opts):
     """Sets tf_msda_set_option knobs; returns the previous values (pass them back to restore)."""
     L = lib()
     return {k: L.tf_msda_set_option(k.encode(), int(v)) for k, v in opts.items()}
+
+
+def last_kernel():
+    """Name of the kernel the most recent MSDA call dispatched to (tf_msda_last_kernel)."""
+    return lib().tf_msda_last_kernel().decode()
 
 
 def _p(a):

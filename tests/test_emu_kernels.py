@@ -1282,3 +1282,102 @@ def test_fp16_product_profiles_convolutions(profile):
             U.check(torch.from_numpy(y).reshape(-1, 64), ref, S, floor, nan, fp32=U.conv_fp32(x, wt, bias, 2, 3, relu))
     finally:
         emu_lib.set_terms(prev)
+
+
+# ---- the float64 yardstick (tests/util_msda_numerics.py) on the emulated kernels ------------------------------------------------------------
+# CPU twins of tests/test_msda_numerics_gpu.py at small shapes: every MSDA kernel the emulator builds, the dispatch asserted by name.
+from tests import util_msda_numerics as NU   # noqa: E402
+
+EPYR = [(12, 20), (6, 10), (3, 5), (2, 3)]
+S_EPYR = sum(h * w for h, w in EPYR)
+NU_FWD = [
+    ("rowgather_f32", "msda_fwd_rowgather<f32>", {}, dict(N=2, M=3, D=5, Lq=21, P=3, shapes=[(7, 3), (1, 1), (2, 9)])),
+    ("buf", "msda_fwd_f32_buf<plain>", {}, dict(N=1, M=4, D=64, Lq=30, P=4, shapes=[(12, 10), (6, 5)])),
+    ("direct", "msda_fwd_f32_direct<plain>", {}, dict(N=1, M=8, D=32, Lq=40, P=4, shapes=EPYR)),
+    ("direct9", "msda_fwd_f32_direct9<plain>", {}, dict(N=1, M=8, D=36, Lq=30, P=4, shapes=EPYR * 2)),
+    ("quad", "msda_fwd_f32_quad<plain>", {"tiled": 1, "pquad": 0}, dict(N=1, M=8, D=32, Lq=S_EPYR, P=4, shapes=EPYR, encoder=True)),
+    ("pquad", "msda_fwd_f32_pquad<plain>", {"pquad_v2": 0}, dict(N=1, M=8, D=32, Lq=S_EPYR, P=4, shapes=EPYR, encoder=True)),
+    ("pquad_d36", "msda_fwd_f32_pquad<plain,D=36>", {}, dict(N=1, M=8, D=36, Lq=S_EPYR, P=4, shapes=EPYR, encoder=True)),
+    ("pquad2", "msda_fwd_f32_pquad2<plain,4w,2p>", {}, dict(N=1, M=8, D=32, Lq=S_EPYR, P=4, shapes=EPYR, encoder=True)),
+    ("pquad2_cf", "msda_fwd_f32_pquad2<plain,4w,2p,cf>", {"pquad_cf": 1}, dict(N=1, M=8, D=32, Lq=S_EPYR, P=4, shapes=EPYR, encoder=True)),
+]
+NU_BWD = [
+    ("rowgather_f32", "msda_bwd_rowgather<f32>", dict(N=2, M=3, D=5, Lq=21, P=3, shapes=[(7, 3), (1, 1), (2, 9)])),
+    ("buf", "msda_bwd_f32_buf", dict(N=1, M=4, D=16, Lq=30, P=2, shapes=EPYR)),
+    ("buf_rowatom", "msda_bwd_f32_buf<rowatom>", dict(N=1, M=8, D=32, Lq=40, P=4, shapes=EPYR)),
+    ("sorted2", "msda_bwd_f32_sorted2", dict(N=1, M=8, D=32, Lq=S_EPYR, P=4, shapes=EPYR, encoder=True)),
+]
+NU_FUSED = [
+    ("buf", "msda_fwd_f32_buf<fused>", {}, dict(N=1, M=4, D=16, Lq=30, P=2, shapes=EPYR, ref_dim=4)),
+    ("direct", "msda_fwd_f32_direct<fused>", {}, dict(N=1, M=8, D=32, Lq=40, P=4, shapes=EPYR, ref_dim=2)),
+    ("direct9", "msda_fwd_f32_direct9<fused>", {}, dict(N=1, M=8, D=36, Lq=30, P=4, shapes=EPYR * 2, ref_dim=4)),
+    ("pquad2", "msda_fwd_f32_pquad2<fused,4w,2p>", {}, dict(N=1, M=8, D=32, Lq=S_EPYR, P=4, shapes=EPYR, encoder=True)),
+]
+
+
+def _nu_np(case):
+    return [t.numpy() for t in case]
+
+
+@pytest.mark.parametrize("profile", ["unit", "signed", "small", "level_spread"])
+@pytest.mark.parametrize("cid,kernel,opts,kw", NU_FWD, ids=[c[0] for c in NU_FWD])
+def test_float64_yardstick_forward(cid, kernel, opts, kw, profile):
+    case = NU.make_case(profile, seed=len(cid), **kw)
+    v, s, l, a, _ = _nu_np(case)
+    prev = emu_lib.set_options(**opts)
+    try:
+        out = emu_lib.msda_forward(v, s, l, a)
+        assert emu_lib.last_kernel() == kernel
+    finally:
+        emu_lib.set_options(**prev)
+    NU.check(out, NU.forward_reference(*case[:4]), fp32=msda_oracle.msda_forward(v, s, l, a, nthreads=4), what=kernel)
+
+
+@pytest.mark.parametrize("profile", ["unit", "hot_pixel", "small"])
+@pytest.mark.parametrize("cid,kernel,kw", NU_BWD, ids=[c[0] for c in NU_BWD])
+def test_float64_yardstick_backward(cid, kernel, kw, profile):
+    case = NU.make_case(profile, seed=len(cid), **kw)
+    arrs = _nu_np(case)
+    got = emu_lib.msda_backward(*arrs)
+    assert emu_lib.last_kernel() == kernel
+    rv, rl, ra, left = NU.backward_reference(*case)
+    assert left < NU.EXCLUDE_MAX
+    for g, r, o in zip(got, (rv, rl, ra), msda_oracle.msda_backward(*arrs)):
+        NU.check(g, r, fp32=o, what=kernel)
+
+
+@pytest.mark.parametrize("cid,kernel,opts,kw", NU_FUSED, ids=[c[0] for c in NU_FUSED])
+def test_float64_yardstick_fused(cid, kernel, opts, kw):
+    kw = dict(kw)
+    ref_dim, enc = kw.pop("ref_dim", 2), kw.pop("encoder", False)
+    M, L, P = kw["M"], len(kw["shapes"]), kw["P"]
+    for profile in ("unit", "large_logits"):
+        value, shapes, refp, qproj = NU.make_fused_case(profile, seed=len(cid), ref_dim=ref_dim, encoder=enc, **kw)
+        out = emu_lib.msda_forward_fused(value.numpy(), shapes.numpy(), refp.numpy(), qproj.numpy(), M, L, P)
+        assert emu_lib.last_kernel() == kernel
+        loc, a, dloc, da = NU.fused_locations(shapes, refp, qproj, M, L, P)
+        NU.check(out, NU.forward_reference(value, shapes, loc, a, dloc=dloc, da=da), what=(kernel, profile))
+
+
+@pytest.mark.parametrize("fk,bk,D", [("msda_fwd_f32_direct<plain>", "msda_bwd_f32_buf<rowatom>", 32),
+                                     ("msda_fwd_rowgather<f32>", "msda_bwd_rowgather<f32>", 5)], ids=["direct", "rowgather"])
+def test_float64_yardstick_exact_edges_and_nan_pixels(fk, bk, D):
+    case = NU.exact_edge_case(1, 8, D, 4, [(4, 8), (2, 2), (1, 1), (1, 4)], seed=D)
+    arrs = _nu_np(case)
+    out = emu_lib.msda_forward(*arrs[:4])
+    assert emu_lib.last_kernel() == fk
+    NU.check(out, NU.forward_reference(*case[:4], exact=True))
+    got = emu_lib.msda_backward(*arrs)
+    assert emu_lib.last_kernel() == bk
+    rv, rl, ra, left = NU.backward_reference(*case, exact=True)
+    assert left == 0.0
+    for g, r in zip(got, (rv, rl, ra)):
+        NU.check(g, r)
+    case = list(NU.make_case("unit", 1, 8, D, 60, 4, EPYR, seed=3))
+    NU.add_nan_pixels(case[0], case[2], case[1], 4, seed=1)
+    arrs = _nu_np(case)
+    r = NU.forward_reference(*case[:4])
+    assert bool(r.expect_nan.any())
+    NU.check(emu_lib.msda_forward(*arrs[:4]), r)
+    for g, r in zip(emu_lib.msda_backward(*arrs), NU.backward_reference(*case)[:3]):
+        NU.check(g, r)

@@ -47,6 +47,26 @@ def _bwd(value, shapes, loc, attn, grad_out, host_shapes=True):
     return msda.ms_deform_attn_backward(value, shapes, loc, attn, grad_out, 64)
 
 
+def _f64_forward(out, value, shapes, loc, attn, ref32):
+    """The float64 yardstick (tests/util_msda_numerics.py) next to the fp32 oracle comparison; ref32: the oracle's output."""
+    from tests import util_msda_numerics as NU
+    return NU.check(out, NU.forward_reference(value, shapes.cpu(), loc, attn), fp32=ref32)
+
+
+def _f64_backward(grads, value, shapes, loc, attn, grad_out, refs32, random_positions=True):
+    """random_positions=False: positions on a pixel grid ("init"), many grad_loc coordinates sit on a cell edge and are left out."""
+    from tests import util_msda_numerics as NU
+    rv, rl, ra, left = NU.backward_reference(value, shapes.cpu(), loc, attn, grad_out)
+    assert left < (NU.EXCLUDE_MAX if random_positions else 1.0)
+    for g, r, o in zip(grads, (rv, rl, ra), refs32):
+        NU.check(g, r, fp32=o)
+
+
+def _kernel():
+    from trackformer_amd import msda
+    return msda.last_kernel()
+
+
 def _to_dev(z, dev):
     t = {k: torch.from_numpy(v).to(dev) for k, v in z.items()}
     return t["value"], t["shapes"], t["loc"], t["attn"], t["grad_out"]
@@ -156,10 +176,12 @@ def _cfg2(dev, Lq, seed=0, loc_mode="rand", N=1):
                          ids=["encoder_rand", "encoder_local", "decoder_wide"])
 def test_full_size_cfg2_vs_oracle(dev, Lq, loc_mode):
     value, shapes, loc, attn, grad_out = _cfg2(dev, Lq, seed=5, loc_mode=loc_mode)
-    out = _fwd(value, shapes, loc, attn).cpu().numpy()
+    out_t = _fwd(value, shapes, loc, attn)
+    out = out_t.cpu().numpy()
     ref = msda_oracle.msda_forward(value.cpu().numpy(), shapes.cpu().numpy(), loc.cpu().numpy(),
                                    attn.cpu().numpy(), nthreads=8)
     np.testing.assert_allclose(out, ref, atol=1e-5, rtol=1e-4)
+    _f64_forward(out_t, value, shapes, loc, attn, ref)
 
 
 def test_full_size_cfg2_backward_vs_oracle(dev):
@@ -172,16 +194,20 @@ def test_full_size_cfg2_backward_vs_oracle(dev):
     np.testing.assert_allclose(gv, rv, atol=2e-4, rtol=1e-4)
     np.testing.assert_allclose(gl, rl, atol=2e-3, rtol=1e-4)  # values are O(100) (scaled by W_l, H_l)
     np.testing.assert_allclose(ga, ra, atol=1e-4, rtol=1e-4)
+    _f64_backward((gv, gl, ga), value, shapes, loc, attn, grad_out, (rv, rl, ra))
 
 
 def test_full_size_cfg4_multiframe_decoder_vs_oracle(dev):
     # cfg 4: hidden 288 (D=36), 8 decoder levels (2 frames), Lq = 500 + 300
     value, shapes, loc, attn, _ = rand_inputs(9, N=1, M=8, D=36, Lq=800, P=4,
                                               shapes=CFG2_SHAPES * 2, loc_mode="wide", device=dev)
-    out = _fwd(value, shapes, loc, attn).cpu().numpy()
+    out_t = _fwd(value, shapes, loc, attn)
+    assert _kernel() == "msda_fwd_f32_direct9<plain>"
+    out = out_t.cpu().numpy()
     ref = msda_oracle.msda_forward(value.cpu().numpy(), shapes.cpu().numpy(), loc.cpu().numpy(),
                                    attn.cpu().numpy(), nthreads=8)
     np.testing.assert_allclose(out, ref, atol=1e-5, rtol=1e-4)
+    _f64_forward(out_t, value, shapes, loc, attn, ref)
 
 
 def test_full_size_properties(dev):
@@ -484,10 +510,12 @@ def test_persistent_encoder_kernel_variants_vs_oracle(dev, opts):
     try:
         shapes_l = [(40, 61), (20, 31), (10, 16), (5, 8)]
         value, shp, loc, attn, _ = _encoder_inputs(dev, shapes_l, "local", N=2, seed=11)
-        out = _fwd(value, shp, loc, attn).cpu().numpy()
+        out_t = _fwd(value, shp, loc, attn)
+        out = out_t.cpu().numpy()
         ref = msda_oracle.msda_forward(value.cpu().numpy(), shp.cpu().numpy(), loc.cpu().numpy(),
                                        attn.cpu().numpy(), nthreads=8)
         np.testing.assert_allclose(out, ref, atol=1e-5, rtol=1e-4)
+        _f64_forward(out_t, value, shp, loc, attn, ref)
         # fused entry on the same geometry: raw offsets / logits + encoder reference points
         N, S, M, D = value.shape
         L, P = len(shapes_l), 4
@@ -560,6 +588,7 @@ def test_encoder_shape_backward_vs_oracle(dev, name, shapes, mode, N, M, D):
     np.testing.assert_allclose(gv, rv, atol=2e-4, rtol=1e-4)
     np.testing.assert_allclose(gl, rl, atol=2e-3, rtol=1e-4)
     np.testing.assert_allclose(ga, ra, atol=1e-4, rtol=1e-4)
+    _f64_backward((gv, gl, ga), value, shp, loc, attn, grad_out, (rv, rl, ra), random_positions=mode != "init")
 
 
 # ------------------------------------------------------------------ fused prologue (inference)
@@ -639,7 +668,9 @@ def test_direct9_decoder_kernel(dev, Lq, L, N):
     prev = lib.tf_msda_set_option(b"direct9", 1)
     try:
         out = _fwd(value, shapes, loc, attn)
+        assert _kernel() == "msda_fwd_f32_direct9<plain>"
         np.testing.assert_allclose(out.cpu().numpy(), ref, atol=1e-5, rtol=1e-4)
+        _f64_forward(out, value, shapes, loc, attn, ref)
         assert torch.allclose(out, base, atol=2e-6, rtol=1e-5)
         assert torch.equal(_fwd(value, shapes.clone(), loc, attn, host_shapes=False), out)
         g = torch.Generator().manual_seed(Lq)
@@ -655,6 +686,7 @@ def test_direct9_decoder_kernel(dev, Lq, L, N):
                 floc = refp[:, :, None, :, None, :2] + off / P * refp[:, :, None, :, None, 2:] * 0.5
             expect = msda_oracle.msda_forward(value.cpu().numpy(), shapes.cpu().numpy(), floc.numpy(), a.numpy(), nthreads=8)
             got = msda.ms_deform_attn_forward_fused(value, shapes, refp.to(dev), qproj.to(dev), M, L, P)
+            assert _kernel() == "msda_fwd_f32_direct9<fused>"
             np.testing.assert_allclose(got.cpu().numpy(), expect, atol=2e-5, rtol=1e-4)
     finally:
         lib.tf_msda_set_option(b"direct9", prev)
@@ -672,7 +704,9 @@ def test_backward_sorted_kernel_with_points_outside_their_windows(dev, name, sha
     rv, rl, ra = msda_oracle.msda_backward(value.cpu().numpy(), shp.cpu().numpy(), loc.cpu().numpy(),
                                            attn.cpu().numpy(), grad_out.cpu().numpy())
     gv, gl, ga = [t.cpu().numpy() for t in _bwd(value, shp, loc, attn, grad_out)]
+    assert _kernel() == "msda_bwd_f32_sorted2" or name == "coarse_first_falls_back"
     np.testing.assert_allclose(gv, rv, atol=2e-4, rtol=1e-4)
     np.testing.assert_allclose(gl, rl, atol=2e-3, rtol=1e-4)
     np.testing.assert_allclose(ga, ra, atol=1e-4, rtol=1e-4)
+    _f64_backward((gv, gl, ga), value, shp, loc, attn, grad_out, (rv, rl, ra), random_positions=mode != "init")
 

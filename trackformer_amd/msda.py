@@ -203,19 +203,37 @@ def ms_deform_attn_forward_fused(value, spatial_shapes, reference_points, qproj,
     if hs is None:
         raise RuntimeError("ms_deform_attn_forward_fused needs host-side level shapes "
                            "(attach_host_shapes)")
+    if value.dim() != 4 or qproj.dim() != 3 or reference_points.dim() != 4:
+        raise RuntimeError("ms_deform_attn_forward_fused: expected value[N,S,M,D], reference_points[N,Lq,L,2|4], "
+                           "qproj[N,Lq,3*M*L*P]")
+    for name, t in (("value", value), ("reference_points", reference_points), ("qproj", qproj)):
+        if t.dtype != torch.float32:
+            raise RuntimeError("ms_deform_attn_forward_fused: %s must be float32, got %s" % (name, t.dtype))
+        if not t.is_cuda or t.device != value.device:
+            raise RuntimeError("ms_deform_attn_forward_fused: %s must be a CUDA tensor on value's device" % name)
+    if not value.is_contiguous():
+        raise RuntimeError("ms_deform_attn_forward_fused: value tensor has to be contiguous")
     N, S, M, D = value.shape
     Lq = qproj.shape[1]
     L, P = n_levels, n_points
-    if M != n_heads or qproj.shape[-1] != 3 * M * L * P or reference_points.shape[:3] != (N, Lq, L):
+    if M != n_heads or qproj.shape[-1] != 3 * M * L * P or qproj.shape[0] != N \
+            or tuple(reference_points.shape[:3]) != (N, Lq, L):
         raise RuntimeError("ms_deform_attn_forward_fused: inconsistent tensor shapes")
     reference_points = reference_points.contiguous()
+    # the kernels read row (b, q) of qproj at (b * Lq + q) * ld: a view whose columns are adjacent and whose batches are Lq rows
+    # apart (a column slice of a wider projection) is passed with its row stride, anything else as a contiguous copy
+    ld = qproj.stride(1)
+    if not (Lq > 1 and qproj.stride(2) == 1 and (N == 1 or qproj.stride(0) == Lq * ld) and ld >= qproj.shape[-1]
+            and ld % 2 == 0 and qproj.data_ptr() % 8 == 0):
+        qproj = qproj.contiguous()
+        ld = qproj.shape[-1]
     lib = _cabi.lib()
     with torch.cuda.device(value.device):
         out = torch.empty((N, Lq, M * D), dtype=value.dtype, device=value.device)
         arr = _shape_array(hs)
         rc = lib.tf_msda_forward_fused_f32(
             value.data_ptr(), ctypes.cast(arr, ctypes.c_void_p), reference_points.data_ptr(),
-            reference_points.shape[-1], qproj.data_ptr(), qproj.shape[-1], 0, 2 * M * L * P,
+            reference_points.shape[-1], qproj.data_ptr(), ld, 0, 2 * M * L * P,
             out.data_ptr(), N, S, M, D, L, Lq, P, torch.cuda.current_stream().cuda_stream)
     _cabi.check(rc, "ms_deform_attn_forward_fused")
     return out
