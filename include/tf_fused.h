@@ -78,8 +78,10 @@ int tf_postprocess_pack_f32(const float *logits, const float *boxes, float *out,
  */
 int tf_groupnorm_nhwc_f32(const float *x, const float *gamma, const float *beta, float *out, double *workspace, int N,
                           int HW, int C, int G, float eps, int64_t x_image_stride, int64_t out_image_stride, void *stream);
-/* The statistics pass alone: workspace[n][g] = (sum, sum of squares) of x's group g of image n, as doubles -- for a consumer that applies
- * the normalisation in its own fetch (tf_conv3x3_merge_packed_f32). */
+/* The statistics pass alone: workspace[n][g] = (sum, sum of squares) of x's group g of image n, as doubles: every element is widened
+ * to double BEFORE it is squared and summed, so that var = sumsq / cnt - mean^2 (formed in double by the consumers) keeps the variance
+ * of a group whose |mean| is thousands of times its spread -- for a consumer that applies the normalisation in its own fetch
+ * (tf_conv3x3_merge_packed_f32). */
 int tf_groupnorm_stats_nhwc_f32(const float *x, double *workspace, int N, int HW, int C, int G, int64_t x_image_stride, void *stream);
 /* The same followed by ReLU in the same pass: `F.relu(gn(conv(x)))` of the mask head (reference: models/detr_segmentation.py:142-156). */
 int tf_groupnorm_relu_nhwc_f32(const float *x, const float *gamma, const float *beta, float *out, double *workspace, int N,

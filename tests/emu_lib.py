@@ -376,18 +376,41 @@ def bias_relu_maxpool(x_nhwc, bias):
     return out
 
 
-def mha_core(q, k, v, scale, key_mask=None):
-    """q [N, Lq, H, D], k / v [N, Lk, H, D] -> out [N, Lq, H, D]."""
+def _strided(a, ld, fill=np.nan, guard_rows=0):
+    """a [N, L, E] -> a 16-byte aligned [N * L + guard_rows, ld] buffer holding a's rows in its first E columns, `fill` elsewhere."""
+    N, L, E = a.shape
+    buf = _aligned(np.full((N * L + guard_rows, ld), fill, np.float32))
+    buf[:N * L, :E] = a.reshape(N * L, E)
+    return buf
+
+
+MHA_CANARY = np.float32(-1234.5)
+
+
+def mha_core(q, k, v, scale, key_mask=None, ldq=None, ldk=None, ldv=None, ldo=None, packed_qk=False):
+    """q [N, Lq, H, D], k / v [N, Lk, H, D] -> out [N, Lq, H, D].  ld* (floats, >= H * D): the operand's rows lie that far apart in
+    a buffer whose gaps hold NaN (out: a canary, also in 3 rows behind the last; checked unchanged).  packed_qk: q | k side by side
+    in ONE buffer (ld 2 H D; Lq == Lk), as the decoder's shared projection leaves them."""
     q, k, v = _c(q, np.float32), _c(k, np.float32), _c(v, np.float32)
     N, Lq, H, D = q.shape
-    Lk = k.shape[1]
-    out = np.full(q.shape, np.nan, np.float32)
+    Lk, E = k.shape[1], H * D
+    ldq, ldk, ldv, ldo = ldq or E, ldk or E, ldv or E, ldo or E
+    if packed_qk:
+        assert Lq == Lk
+        ldq = ldk = 2 * E
+        qk = _strided(np.concatenate([q.reshape(N, Lq, E), k.reshape(N, Lk, E)], -1), 2 * E)
+        qp, kp = qk.ctypes.data, qk.ctypes.data + 4 * E
+    else:
+        qb, kb = _strided(q.reshape(N, Lq, E), ldq), _strided(k.reshape(N, Lk, E), ldk)
+        qp, kp = qb.ctypes.data, kb.ctypes.data
+    vb = _strided(v.reshape(N, Lk, E), ldv)
+    ob = _strided(np.full((N, Lq, E), np.nan, np.float32), ldo, MHA_CANARY, guard_rows=3)
     km = np.ascontiguousarray(key_mask, dtype=np.uint8) if key_mask is not None else None
-    rc = lib().tf_mha_core_f32(_p(q), _p(k), _p(v), _p(out), _p(km), N, Lq, Lk, H, D, H * D, H * D, H * D, H * D,
-                               ctypes.c_float(scale), None)
+    rc = lib().tf_mha_core_f32(qp, kp, _p(vb), _p(ob), _p(km), N, Lq, Lk, H, D, ldq, ldk, ldv, ldo, ctypes.c_float(scale), None)
     if rc != 0:
         raise RuntimeError("tf_mha_core_f32: status %d" % rc)
-    return out
+    assert (ob[:N * Lq, E:] == MHA_CANARY).all() and (ob[N * Lq:] == MHA_CANARY).all(), "tf_mha_core_f32 wrote outside its rows"
+    return ob[:N * Lq, :E].reshape(N, Lq, H, D).copy()
 
 
 def bias_act(x, bias, residual=None, relu=True):
@@ -493,14 +516,17 @@ def conv3x3_splitk(x_nhwc, w_ohwi, bias=None, relu=False, stride=1, ksplit=4):
     return y
 
 
-def groupnorm_nhwc(x, gamma, beta, G, eps=1e-5, relu=False):
-    """x [N, HW, C] -> GroupNorm over (HW, C / G) per image and group [+ ReLU: tf_groupnorm_relu_nhwc_f32]."""
-    x, gamma, beta = _c(x, np.float32), _c(gamma, np.float32), _c(beta, np.float32)
+def groupnorm_nhwc(x, gamma, beta, G, eps=1e-5, relu=False, gap=0):
+    """x [N, HW, C] -> GroupNorm over (HW, C / G) per image and group [+ ReLU: tf_groupnorm_relu_nhwc_f32].  gap (floats, a multiple
+    of 4): the images of x lie HW * C + gap apart with NaN between them (x_image_stride)."""
+    x, gamma, beta = _c(x, np.float32), _aligned(gamma), _aligned(beta)
     n, hw, c = x.shape
-    out = np.full(x.shape, np.nan, np.float32)
+    xs = _aligned(np.full((n, hw * c + gap), np.nan, np.float32))
+    xs[:, :hw * c] = x.reshape(n, hw * c)
+    out = _aligned(np.full(x.shape, np.nan, np.float32))
     ws = np.full(2 * n * G, np.nan, np.float64)
     fn = lib().tf_groupnorm_relu_nhwc_f32 if relu else lib().tf_groupnorm_nhwc_f32
-    rc = fn(_p(x), _p(gamma), _p(beta), _p(out), _p(ws), n, hw, c, G, ctypes.c_float(eps), hw * c, hw * c, None)
+    rc = fn(_p(xs), _p(gamma), _p(beta), _p(out), _p(ws), n, hw, c, G, ctypes.c_float(eps), hw * c + gap, hw * c, None)
     if rc != 0:
         raise RuntimeError("tf_groupnorm_nhwc_f32: status %d" % rc)
     return out

@@ -552,7 +552,8 @@ def test_conv3x3_as_split_product(n, h, w, cin, cout, stride, ks, terms):
 
 @pytest.mark.parametrize("n,hw,c,g", [(1, 300, 256, 32), (2, 77, 288, 32), (1, 1, 64, 8), (3, 129, 32, 4)], ids=lambda v: str(v))
 def test_groupnorm_nhwc(n, hw, c, g):
-    """tf_groupnorm_nhwc_f32 (statistics per image and group over HW x C / G, double accumulation) against numpy float64."""
+    """tf_groupnorm_nhwc_f32 (statistics per image and group over HW x C / G: every element widened to double before it is
+    squared and summed) against numpy float64."""
     rng = np.random.default_rng(hw + c)
     x = (rng.standard_normal((n, hw, c), dtype=np.float32) * 3 + 1.5).astype(np.float32)
     ga, be = rng.standard_normal(c, dtype=np.float32), rng.standard_normal(c, dtype=np.float32)

@@ -228,6 +228,13 @@ def test_linear_residual_layernorm(rows, ti, d, monkeypatch):
         lib.tf_msda_set_option(b"linln_ti", prev_ti)
     assert got is not None
     assert torch.allclose(got, ref, atol=1e-5, rtol=1e-5)
+    # and against float64 of the whole chain (tests/util_split_numerics.py): the projection's bound carried through the LayerNorm
+    from tests import util_split_numerics as U
+    x2, r2 = x.reshape(rows, d), res.reshape(rows, d)
+    pre, S, floor, nan = U.linear_reference(x2, lin.weight.detach(), lin.bias.detach(), r2, terms=fused.split_terms())
+    ref_ln, S_ln, floor_ln, nan_ln = U.layernorm_reference(pre, S, floor, norm.weight.detach(), norm.bias.detach(), norm.eps, nan)
+    worst = U.check(got.reshape(rows, d), ref_ln, S_ln, floor_ln, nan_ln)
+    print("EXCESS linear_res_ln %dx%d ti %d: %s" % (rows, d, ti, worst))
 
 
 @pytest.mark.parametrize("shape", [(1, 64, 400, 667), (2, 64, 33, 20), (1, 8, 7, 9)])

@@ -125,7 +125,7 @@ bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 
 
 // ---- GroupNorm over channels-innermost activations: x [N, HW, C] (the storage of a channels_last NCHW tensor, or a
 // token-major projection output), statistics per (image, group) over HW x (C / G) elements.  Two passes:
-//   groupnorm_stats_kernel   partial sums per workgroup (fp32 over <= 64 rows per thread, then double), one double
+//   groupnorm_stats_kernel   partial sums per workgroup (every element widened to double before it is squared and summed), one double
 //                            atomic per group and workgroup into ws[n][g][sum | sum of squares]
 //   groupnorm_apply_kernel   y = (x - mean) * rstd * gamma + beta, mean / rstd from ws (double arithmetic, once per
 //                            workgroup into LDS), 16 bytes per lane
@@ -153,35 +153,38 @@ groupnorm_stats_kernel(const float *__restrict__ x, double *__restrict__ ws, int
     const int q = threadIdx.x % C4, rslot = threadIdx.x / C4;
     if (rslot < nslots) {
         const f32x4_t *xp = reinterpret_cast<const f32x4_t *>(x + (long long)n * x_image_stride);
-        f32x4_t sum = {0.f, 0.f, 0.f, 0.f}, sq = {0.f, 0.f, 0.f, 0.f};
+        // every element is widened before it is squared and summed: fp32 sums of squares lose the variance of a group whose
+        // |mean| is far above its spread (E[x^2] - mean^2 cancels: off by 1e-2 at |mean| = 300 std, noise at 3000).  Measured on
+        // MI355X against the fp32 partial sums it replaces (rocprofv3, 13 runs of 200 launches each, input resident in cache): 8.9 us
+        // for 8.5 at (1, 16700, 256, 32), 11.5 for 11.2 at (100, 4200, 32, 8), 3.3 for 3.1 at (100, 273, 128, 8); frames/s of cfg 2
+        // and cfg 5 unchanged.  fp32 sums shifted by a per-group pivot x[n, 0, first channel] (no double arithmetic per element)
+        // were measured too: 14.0 / 13.8 / 3.6 us -- the dependent pivot loads cost more than the conversions.
+        double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0, q0 = 0.0, q1 = 0.0, q2 = 0.0, q3 = 0.0;
+        auto acc = [&](const f32x4_t &v) {
+            const double a = (double)v.x, b = (double)v.y, c = (double)v.z, d = (double)v.w;
+            s0 += a; s1 += b; s2 += c; s3 += d;
+            q0 = fma(a, a, q0); q1 = fma(b, b, q1); q2 = fma(c, c, q2); q3 = fma(d, d, q3);
+        };
         int r = r0 + rslot;
         for (; r + 3 * nslots < r1; r += 4 * nslots) {   // four rows in flight per thread, accumulated in row order
             const f32x4_t v0 = xp[(long long)r * C4 + q], v1 = xp[(long long)(r + nslots) * C4 + q];
             const f32x4_t v2 = xp[(long long)(r + 2 * nslots) * C4 + q], v3 = xp[(long long)(r + 3 * nslots) * C4 + q];
-            sum += v0;
-            sq += v0 * v0;
-            sum += v1;
-            sq += v1 * v1;
-            sum += v2;
-            sq += v2 * v2;
-            sum += v3;
-            sq += v3 * v3;
+            acc(v0);
+            acc(v1);
+            acc(v2);
+            acc(v3);
         }
-        for (; r < r1; r += nslots) {
-            const f32x4_t v = xp[(long long)r * C4 + q];
-            sum += v;
-            sq += v * v;
-        }
+        for (; r < r1; r += nslots) acc(xp[(long long)r * C4 + q]);
         // the four channels of a quad may straddle two groups (hidden 288: 9 channels per group)
         const int g0 = (q * 4) / cpg, g1 = (q * 4 + 1) / cpg, g2 = (q * 4 + 2) / cpg, g3 = (q * 4 + 3) / cpg;
         if (g0 == g3) {
-            atomicAdd(&s_stat[2 * g0], (double)((sum.x + sum.y) + (sum.z + sum.w)));
-            atomicAdd(&s_stat[2 * g0 + 1], (double)((sq.x + sq.y) + (sq.z + sq.w)));
+            atomicAdd(&s_stat[2 * g0], (s0 + s1) + (s2 + s3));
+            atomicAdd(&s_stat[2 * g0 + 1], (q0 + q1) + (q2 + q3));
         } else {
-            atomicAdd(&s_stat[2 * g0], (double)sum.x); atomicAdd(&s_stat[2 * g0 + 1], (double)sq.x);
-            atomicAdd(&s_stat[2 * g1], (double)sum.y); atomicAdd(&s_stat[2 * g1 + 1], (double)sq.y);
-            atomicAdd(&s_stat[2 * g2], (double)sum.z); atomicAdd(&s_stat[2 * g2 + 1], (double)sq.z);
-            atomicAdd(&s_stat[2 * g3], (double)sum.w); atomicAdd(&s_stat[2 * g3 + 1], (double)sq.w);
+            atomicAdd(&s_stat[2 * g0], s0); atomicAdd(&s_stat[2 * g0 + 1], q0);
+            atomicAdd(&s_stat[2 * g1], s1); atomicAdd(&s_stat[2 * g1 + 1], q1);
+            atomicAdd(&s_stat[2 * g2], s2); atomicAdd(&s_stat[2 * g2 + 1], q2);
+            atomicAdd(&s_stat[2 * g3], s3); atomicAdd(&s_stat[2 * g3 + 1], q3);
         }
     }
     __syncthreads();

@@ -808,7 +808,7 @@ def groupnorm_nhwc(x2, n_img, gn, relu=False):
     """GroupNorm [+ ReLU] of x2 [n_img * HW, C] (channels innermost) with nn.GroupNorm `gn`'s parameters; returns a new tensor of
     the same shape or None when the kernel does not apply."""
     if not (x2.is_cuda and x2.dtype == torch.float32 and x2.dim() == 2 and x2.is_contiguous()
-            and gn.weight is not None and gn.bias is not None and gn.weight.device == x2.device):
+            and gn.weight is not None and gn.bias is not None and _param_ok(gn.weight, x2) and _param_ok(gn.bias, x2)):
         return None
     rows, c = x2.shape
     if rows % n_img or c != gn.num_channels or c % 4 or c > 1024 or gn.num_groups > 256 or n_img > 65535 or (x2.data_ptr() & 15):
@@ -920,7 +920,9 @@ def groupnorm_relu_conv3x3_c1(x, gn, conv):
             and x.shape[1] in (16, 32) and gn.num_channels == x.shape[1] and gn.weight is not None and gn.bias is not None
             and conv.out_channels == 1 and conv.in_channels == x.shape[1] and conv.kernel_size == (3, 3) and conv.stride == (1, 1)
             and conv.padding == (1, 1) and conv.dilation == (1, 1) and conv.groups == 1 and x.shape[0] <= 65535
-            and gn.weight.device == x.device and conv.weight.device == x.device and not (x.data_ptr() & 15)):
+            and _param_ok(gn.weight, x) and _param_ok(gn.bias, x) and conv.weight.device == x.device
+            and conv.weight.dtype == torch.float32 and (conv.bias is None or conv.bias.dtype == torch.float32)
+            and not (x.data_ptr() & 15)):
         return None
     n, c, H, W = x.shape
     hit = getattr(conv, "_tf_c1_taps", None)   # [9, C] tap-major + the bias as a Python float (one synchronising read per weight version)
@@ -1075,7 +1077,9 @@ def mha_core(qk, v, num_heads, key_padding_mask=None):
         return None
     mask_ptr = 0
     if key_padding_mask is not None:
-        if key_padding_mask.shape != (n, length) or key_padding_mask.device != qk.device:
+        # bool / uint8 only (non-zero = ignore): a float mask is ADDITIVE for nn.MultiheadAttention (-inf = ignore, 0 = keep)
+        if (key_padding_mask.shape != (n, length) or key_padding_mask.device != qk.device
+                or key_padding_mask.dtype not in (torch.bool, torch.uint8)):
             return None
         key_padding_mask = key_padding_mask.to(torch.uint8).contiguous()
         mask_ptr = key_padding_mask.data_ptr()
