@@ -36,6 +36,10 @@ extern "C" {
  * x[i] = act(x[i] + bias[i % C] + (residual ? residual[i] : 0)),  act = ReLU if relu != 0 else identity.
  * x / residual: `n` floats, channel-innermost (NHWC storage of a channels_last tensor), in place on x.
  * C % 4 == 0 and 16-byte aligned pointers are required.
+ * Non-finite operands: plain IEEE additions in the order (x + bias) + residual, each rounded to fp32; ReLU is `v < 0 ? 0 : v`, which
+ * keeps NaN and -0.0.  That is torch.relu on the CPU; on MI355X torch.relu(-0.0) is +0.0, so there the result differs from the ATen
+ * chain in the sign of such zeros (and in nothing else).  residual must not overlap x (the kernel's pointers are restrict-qualified);
+ * residual == x is refused.
  */
 int tf_bias_act_f32(float *x, const float *bias, const float *residual, int64_t n, int C, int relu,
                     void *stream);
@@ -62,6 +66,9 @@ int tf_box_refine_f32(const float *delta, const float *ref, float *out, int64_t 
  * clip_boxes_to_image and the stacking of what the association reads).  logits [Q, C], boxes [Q, 4] (cx, cy, w, h in [0, 1]),
  * out [Q, 6] = (x0, y0, x1, y1, score, label as float):
  *   score = max_c sigmoid(logits[q, c]), label = the first c that attains it;
+ *   non-finite logits as `sigmoid().max(-1)`: +inf scores exactly 1, -inf exactly 0; a NaN logit in ANY class makes the score NaN and
+ *   the label the FIRST class whose logit is NaN (torch.max, on the CPU and on the device); the boxes are independent of the logits,
+ *   and fminf / fmaxf turn a NaN coordinate into 0 when clip != 0 (torch.clamp would keep it: boxes are expected to be finite);
  *   x0 = (cx - 0.5 w) img_w, y0 = (cy - 0.5 h) img_h, x1 = (cx + 0.5 w) img_w, y1 = (cy + 0.5 h) img_h, every operation rounded
  *   on its own (no fused multiply-add: the arithmetic of the separate ATen kernels), then, if clip != 0, clamped to [0, img_w] /
  *   [0, img_h].  Replaces ~17 element-wise launches on [Q, 4] tensors per frame.
@@ -92,7 +99,9 @@ int tf_groupnorm_relu_nhwc_f32(const float *x, const float *gamma, const float *
  * F.interpolate(x, size=fpn.shape[-2:], mode="nearest")`): out[n, y, x, c] = low[n, ys, xs, c] + fpn[n / q_per_image, y, x, c] with
  * ys = min(floorf(y * (float)h / H), h - 1), xs likewise (torch's legacy "nearest" index).  low [N, h, w, C], fpn [N / q_per_image, H,
  * W, C], out [N, H, W, C] -- the storage of channels_last NCHW tensors; C % 4 == 0, 16-byte aligned.  The reference's two passes
- * write and re-read the up-sampled tensor (1.1 GB per 128 queries at the finest level of an 800 x 1333 frame).
+ * write and re-read the up-sampled tensor (1.1 GB per 128 queries at the finest level of an 800 x 1333 frame).  Any size pair (up-,
+ * down-sampling, identity).  Non-finite operands: one IEEE addition per element (NaN and inf - inf = NaN propagate), bit-identical to
+ * the two ATen passes.
  */
 int tf_upsample_add_nhwc_f32(const float *low, const float *fpn, float *out, int N, int q_per_image, int h, int w, int H, int W, int C,
                              void *stream);
@@ -129,6 +138,10 @@ int tf_groupnorm_relu_conv3x3_c1_nhwc_f32(const float *x, const float *gamma, co
  * track has none); label [out_h, out_w] int16: the owning track's index or -1.  Per output pixel: its nearest source pixel in the
  * (img_h, img_w) crop of the (pad_h, pad_w) grid (torch's legacy "nearest" index), there the bilinear sample of every track's logits
  * (align_corners = False, torch's arithmetic operation by operation), its sigmoid; ties go to the first track, as torch.max.
+ * n_tracks <= 32767, img <= pad in both directions; any threshold.  Non-finite logits as the chain `stack -> max -> best > threshold`
+ * has them: a pixel where ANY track's probability is NaN (a NaN logit under one of its four taps, inf - inf between taps, or 0 * inf
+ * at a tap of weight exactly 0) is -1, because torch.max returns the NaN and NaN > threshold is false; +inf samples give probability
+ * exactly 1, -inf exactly 0.
  * The reference's chain writes and re-reads n full-size fp32 maps (~0.9 GB per frame at 100 tracks and 1080 x 1920).
  */
 int tf_mask_label_map_f32(const float *logits, const int *order, int16_t *label, int n_tracks, int h, int w, int pad_h, int pad_w, int img_h,
@@ -223,8 +236,12 @@ int tf_stem_conv7x7_f32(const float *x, const void *w_packed, const float *bias,
  * out[n, oy, ox, c] = max over the 3 x 3 window (stride 2, padding 1) of relu(x[n, iy, ix, c] + bias[c]) on channels_last
  * activations: FrozenBatchNorm2d shift + ReLU + MaxPool2d(3, 2, 1) after the backbone's first convolution (reference:
  * models/backbone.py:45-55, torchvision ResNet.relu / .maxpool) in one pass.  x [N, H, W, C], out [N, (H - 1) / 2 + 1,
- * (W - 1) / 2 + 1, C], C % 4 == 0, 16-byte aligned pointers.  Bit-identical to the separate passes (the shift and the ReLU
- * are monotone per channel).
+ * (W - 1) / 2 + 1, C], C % 4 == 0, 16-byte aligned pointers, fewer than 2^31 output quads.  Bit-identical to the separate passes,
+ * non-finite operands included: the shift is added to every window element before the maximum, a NaN anywhere in the window (NaN
+ * input, NaN shift, -inf under a shift of +inf) is the window's maximum as in torch's max_pool2d, and the ReLU (`v < 0 ? 0 : v`)
+ * keeps it.  Zeros: the ReLU keeps -0.0 (relu(-0.0 + -0.0) = -0.0), which is torch.relu on the CPU; torch.relu on MI355X returns +0.0
+ * there, so against the ATen chain ON THE DEVICE the output differs in the sign of such zeros and in nothing else.  The sign of a zero
+ * maximum over a window that holds both +0.0 and -0.0 follows the order of the scan and is not part of the contract.
  */
 int tf_bias_relu_maxpool_f32(const float *x, const float *bias, float *out, int N, int H, int W, int C, void *stream);
 

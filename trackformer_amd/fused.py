@@ -23,14 +23,14 @@ def _param_ok(t, x):
 
 def bias_act_(x, bias, residual=None, relu=True):
     """In place: x = act(x + bias[c] (+ residual)) for a channels_last [N,C,H,W] fp32 GPU tensor.
-    Returns x, or None when the tensors do not qualify (caller falls back to ATen ops)."""
+    Returns x, or None when the tensors do not qualify -- a residual that is x itself included -- (caller falls back to ATen ops)."""
     if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
             and x.is_contiguous(memory_format=torch.channels_last)):
         return None
     C = x.shape[1]
     if C % 4 or not _param_ok(bias, x) or x.data_ptr() % 16:
         return None
-    if residual is not None and not (residual.shape == x.shape and residual.dtype == x.dtype
+    if residual is not None and not (residual.data_ptr() != x.data_ptr() and residual.shape == x.shape and residual.dtype == x.dtype
                                      and residual.device == x.device and residual.data_ptr() % 16 == 0
                                      and residual.is_contiguous(memory_format=torch.channels_last)):
         return None
@@ -826,8 +826,8 @@ def groupnorm_nhwc(x2, n_img, gn, relu=False):
 
 def mask_label_map(logits, order, pad_hw, img_hw, out_hw, threshold=0.5):
     """The tracker's mask post-processing in one launch (tf_mask_label_map_f32): logits [n, h, w] fp32 on the GPU (mask-head outputs),
-    order: per track the row of `logits` that is its mask (-1: none) -> int16 [out_h, out_w], the owning track per pixel or -1.
-    None when not applicable."""
+    order: per track the row of `logits` that is its mask (-1: none) -> int16 [out_h, out_w], the owning track per pixel or -1 (also
+    where any track's probability is NaN, as `stack -> max -> best > threshold`).  None when not applicable."""
     if not (_postprocess_fused and logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 3 and logits.is_contiguous()
             and 0 < len(order) <= 32767 and logits.numel() > 0):
         return None

@@ -706,7 +706,8 @@ class Tracker:
         """The frame's mask ownership map (int16 [orig_h, orig_w]: index into self.tracks or -1) straight from the mask head's
         low-resolution logits -- PostProcessSegm's bilinear resize / sigmoid / crop / nearest resize and the reference's per-pixel
         argmax over the tracks (tracker.py:521-532) in ONE launch (fused.mask_label_map) instead of ~10 passes over one full-size
-        fp32 map per track.  Lazy mask head on the GPU with the package's own PostProcessSegm only; None otherwise."""
+        fp32 map per track.  Lazy mask head on the GPU with the package's own PostProcessSegm only; None otherwise.  A pixel where
+        any track's probability is NaN is -1, as in the module chain of step() (torch.max returns the NaN, NaN > 0.5 is false)."""
         post = self.obj_detector_post.get('segm')
         if (not self.tracks or 'pred_masks' in outputs or 'mask_context' not in outputs or post is None
                 or type(post).__name__ != "PostProcessSegm" or not type(post).__module__.startswith("trackformer_amd.")
