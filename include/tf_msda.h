@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define TF_MSDA_ABI_VERSION 3
+#define TF_MSDA_ABI_VERSION 4
 #define TF_MSDA_MAX_LEVELS 16
 
 typedef enum tf_msda_status {
@@ -54,7 +54,8 @@ typedef enum tf_msda_status {
     TF_MSDA_ERR_BAD_DIMS = -2,      /* a dimension <= 0, L > TF_MSDA_MAX_LEVELS, or sizes overflow */
     TF_MSDA_ERR_SHAPE_SUM = -3,     /* sum_l H_l*W_l != S (host-shape entry points only) */
     TF_MSDA_ERR_LAUNCH = -4,        /* HIP reported an error enqueueing work (see tf_msda_last_hip_error) */
-    TF_MSDA_ERR_NO_DEVICE = -5      /* no HIP device available */
+    TF_MSDA_ERR_NO_DEVICE = -5,     /* no HIP device available */
+    TF_MSDA_ERR_WORKSPACE = -6      /* caller's workspace smaller than tf_msda_backward_det_workspace_bytes, or misaligned */
 } tf_msda_status;
 
 /* ABI version of the loaded library (== TF_MSDA_ABI_VERSION it was built with). */
@@ -159,7 +160,8 @@ int tf_msda_forward_fused_f32(const float *value, const int64_t *shapes_hw_host,
  * Backward.  Writes all three gradients; grad_value is zero-filled on `stream` by the library before
  * accumulation (reference: at::zeros_like, cu:119-121), grad_loc / grad_attn are fully overwritten.
  * grad_value accumulation uses hardware floating-point atomics, so its summation order (and therefore
- * its last bits) is not deterministic -- as in the reference (cuh:301).
+ * its last bits) is not deterministic -- as in the reference (cuh:301).  tf_msda_backward_det_* below is the
+ * bitwise-reproducible form.
  * replaces ms_deform_attn_cuda_backward (cu:89-168) + ms_deformable_col2im_gpu_kernel (cuh:239-306) +
  * ms_deformable_col2im_coord_gpu_kernel (cuh:308-378).
  */
@@ -179,6 +181,54 @@ int tf_msda_backward_f64_dshapes(const double *value, const int64_t *shapes_hw_d
                                  const double *loc, const double *attn, const double *grad_out,
                                  double *grad_value, double *grad_loc, double *grad_attn, int N,
                                  int S, int M, int D, int L, int Lq, int P, void *stream);
+
+/*
+ * Deterministic backward (opt-in; the entry points above are unchanged).  Same arguments and the same three gradients, computed
+ * without any floating-point atomic (csrc/msda_bwd_det.h): every contribution a * w_c to grad_value is stored once, the
+ * contributions of each (batch, head) block are put in destination-row order by a stable radix sort, and every row is summed
+ * in that fixed order and written once by plain stores.  For a fixed build of the library and a fixed device model grad_value,
+ * grad_loc and grad_attn are a pure function of the tensor contents and the dimensions: bit-identical across repeated calls,
+ * streams, HIP-graph replay, concurrent work on the device, the host-shape / _dshapes entry points, every tf_msda_set_option /
+ * environment knob, and whatever the workspace and the output buffers held on entry.  Two consequences:
+ *   - batch invariance: the gradients of batch element n do not depend on N or on the other elements;
+ *   - no zero-fill pass: every element of grad_value is written exactly once; rows nobody samples get +0.
+ * Accuracy is that of the default kernels (fp32 / fp64 products and sums; only the order of the sums differs).  It is slower
+ * than the default path and meant for reproducing and bisecting training runs.
+ *
+ * workspace: DEVICE memory owned by the caller, 8-byte aligned, at least tf_msda_backward_det_workspace_bytes(...) bytes, not
+ *   shared with a call that may run at the same time; contents on entry are irrelevant, nothing is kept in it between calls.
+ *   Only kernels are enqueued: the call is HIP-graph capturable.
+ * tf_msda_backward_det_workspace_bytes(elem_bytes = 4 | 8, ...): the size, or TF_MSDA_ERR_BAD_DIMS (as int64) for a
+ *   non-positive dimension, L > TF_MSDA_MAX_LEVELS, another elem_bytes, or a block whose 4*Lq*L*P corner slots do not fit 32
+ *   bits.  With I = 4*Lq*L*P (corner slots per (batch, head) block), T = ceil(I / 1024) (radix tiles) and r256 = round up to 256:
+ *       per chunk of nb images:  4 * r256(4 * nb*M*I)              keys and slot indices, double-buffered
+ *                              +     r256(elem_bytes * nb*M*I)     weights
+ *                              +     r256(1024 * nb*M*T)           digit histograms
+ *                              +     r256(4 * nb*M*(S + 1))        row bounds
+ *   nb = the number of images whose workspace fits 512 MiB (at least 1, at most N): the batch is walked nb images at a time,
+ *   which does not change any result.  The 512 MiB are a constant of the build (kDetBatchBudget, csrc/msda_bwd_det.h), not an
+ *   option.  The size therefore depends on EVERY dimension, N included (through nb, until the budget is reached): ask again
+ *   whenever a dimension changes -- a buffer sized for one image is too small for N = 2 where two images fit the budget, and
+ *   the call then returns TF_MSDA_ERR_WORKSPACE.  fp32 at the cfg-2 encoder shape (S = Lq = 22 223, M = 8, L = P = 4): 240 MB per image.
+ * Status: NULL pointer (workspace included) -> TF_MSDA_ERR_NULL_POINTER; dimensions -> TF_MSDA_ERR_BAD_DIMS; a short or misaligned
+ *   workspace -> TF_MSDA_ERR_WORKSPACE; shape sum != S -> TF_MSDA_ERR_SHAPE_SUM -- checked in that order, before any GPU work.
+ * tf_msda_last_kernel() reports "msda_bwd_det<f32>" / "msda_bwd_det<f64>".
+ */
+int64_t tf_msda_backward_det_workspace_bytes(int elem_bytes, int N, int S, int M, int D, int L, int Lq, int P);
+int tf_msda_backward_det_f32(const float *value, const int64_t *shapes_hw_host, const float *loc, const float *attn,
+                             const float *grad_out, float *grad_value, float *grad_loc, float *grad_attn, void *workspace,
+                             int64_t workspace_bytes, int N, int S, int M, int D, int L, int Lq, int P, void *stream);
+int tf_msda_backward_det_f64(const double *value, const int64_t *shapes_hw_host, const double *loc, const double *attn,
+                             const double *grad_out, double *grad_value, double *grad_loc, double *grad_attn, void *workspace,
+                             int64_t workspace_bytes, int N, int S, int M, int D, int L, int Lq, int P, void *stream);
+int tf_msda_backward_det_f32_dshapes(const float *value, const int64_t *shapes_hw_dev, const float *loc, const float *attn,
+                                     const float *grad_out, float *grad_value, float *grad_loc, float *grad_attn,
+                                     void *workspace, int64_t workspace_bytes, int N, int S, int M, int D, int L, int Lq, int P,
+                                     void *stream);
+int tf_msda_backward_det_f64_dshapes(const double *value, const int64_t *shapes_hw_dev, const double *loc, const double *attn,
+                                     const double *grad_out, double *grad_value, double *grad_loc, double *grad_attn,
+                                     void *workspace, int64_t workspace_bytes, int N, int S, int M, int D, int L, int Lq, int P,
+                                     void *stream);
 
 /*
  * The operator for HOST tensors: every pointer is a host pointer, the call computes synchronously on the calling thread

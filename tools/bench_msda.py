@@ -105,8 +105,11 @@ CONFIGS = [
 ]
 
 
-def run(iters=50, modes=("uniform", "local", "init"), device="cuda:0", backward=True, only=None, forward=True):
+def run(iters=50, modes=("uniform", "local", "init"), device="cuda:0", backward=True, only=None, forward=True,
+        deterministic=False):
     rows = []
+    if deterministic:
+        from trackformer_amd import _cabi
     for name, kw in CONFIGS:
         if only and name not in only:
             continue
@@ -128,6 +131,13 @@ def run(iters=50, modes=("uniform", "local", "init"), device="cuda:0", backward=
                 b = algorithmic_bytes(backward=True, **dims)
                 rows.append(dict(shape=name, mode=mode, dir="bwd", ms=ms, alg_MB=b / 1e6,
                                  GBs=b / ms / 1e6, frac=b / ms / 1e6 / HBM_PEAK_GBS))
+            if deterministic:   # the bitwise-reproducible backward (tf_msda_backward_det_*) on the same inputs
+                ms = time_launches(lambda: msda.ms_deform_attn_backward(value, shapes, loc, attn, grad_out, 64,
+                                                                        deterministic=True), iters)
+                b = algorithmic_bytes(backward=True, **dims)
+                ws = _cabi.lib().tf_msda_backward_det_workspace_bytes(4, *[dims[k] for k in ("N", "S", "M", "D", "L", "Lq", "P")])
+                rows.append(dict(shape=name, mode=mode, dir="bwd_det", ms=ms, alg_MB=b / 1e6, GBs=b / ms / 1e6,
+                                 frac=b / ms / 1e6 / HBM_PEAK_GBS, kernel=msda.last_kernel(), workspace_bytes=int(ws)))
     return rows
 
 
@@ -137,6 +147,8 @@ def main():
     ap.add_argument("--json", default=None)
     ap.add_argument("--no-backward", action="store_true")
     ap.add_argument("--no-forward", action="store_true")
+    ap.add_argument("--deterministic", action="store_true",
+                    help="also time the deterministic backward (msda_bwd_det) on the same shapes and modes")
     ap.add_argument("--shapes", default=None, help="comma-separated subset of: " + ", ".join(n for n, _ in CONFIGS))
     ap.add_argument("--modes", default="uniform,local,init")
     ap.add_argument("--option", action="append", default=[], metavar="NAME=VALUE",
@@ -147,7 +159,8 @@ def main():
         k, v = o.split("=")
         print("option %s: %d -> %s" % (k, _cabi.lib().tf_msda_set_option(k.encode(), int(v)), v))
     rows = run(args.iters, modes=tuple(args.modes.split(",")), backward=not args.no_backward,
-               only=args.shapes.split(",") if args.shapes else None, forward=not args.no_forward)
+               only=args.shapes.split(",") if args.shapes else None, forward=not args.no_forward,
+               deterministic=args.deterministic)
     for r in rows:
         print("%-16s %-8s %s  %8.1f us  %7.2f MB  %8.1f GB/s  %5.1f%% of HBM peak" % (
             r["shape"], r["mode"], r["dir"], r["ms"] * 1e3, r["alg_MB"], r["GBs"],

@@ -27,6 +27,11 @@ EXPORTED_SYMBOLS = (
     "tf_msda_backward_f64",
     "tf_msda_backward_f32_dshapes",
     "tf_msda_backward_f64_dshapes",
+    "tf_msda_backward_det_workspace_bytes",
+    "tf_msda_backward_det_f32",
+    "tf_msda_backward_det_f64",
+    "tf_msda_backward_det_f32_dshapes",
+    "tf_msda_backward_det_f64_dshapes",
     "tf_msda_forward_host_f32",
     "tf_msda_forward_host_f64",
     "tf_msda_backward_host_f32",
@@ -62,7 +67,7 @@ EXPORTED_SYMBOLS = (
     "tf_nms_host_f32",
 )
 
-ABI_VERSION = 3   # 3: the split-product entry points take w_lo / w_scale / terms (include/tf_fused.h)
+ABI_VERSION = 4   # 4: tf_msda_backward_det_* and TF_MSDA_ERR_WORKSPACE (3: the split-product entry points take w_lo / w_scale / terms)
 
 _lib = None
 
@@ -107,6 +112,11 @@ def lib():
             b = getattr(L, "tf_msda_backward_%s%s" % (suf, tail))
             b.restype = ci
             b.argtypes = [vp] * 8 + [ci] * 7 + [vp]
+            d = getattr(L, "tf_msda_backward_det_%s%s" % (suf, tail))   # ... + workspace, workspace_bytes
+            d.restype = ci
+            d.argtypes = [vp] * 9 + [ctypes.c_int64] + [ci] * 7 + [vp]
+    L.tf_msda_backward_det_workspace_bytes.restype = ctypes.c_int64
+    L.tf_msda_backward_det_workspace_bytes.argtypes = [ci] * 8
     for suf in ("f32", "f64"):   # host tensors: no stream argument, synchronous
         f = getattr(L, "tf_msda_forward_host_" + suf)
         f.restype = ci

@@ -32,6 +32,8 @@
 //   msda_bwd_f32_buf<P,ROWATOM> fp32 fast path: buffer loads + buffer atomics (full-row scatter for D == 32).
 //   msda_bwd_f32_sorted2        encoder shape, D == 32, P == 4: contributions counting-sorted by destination
 //                               row in LDS, one global atomic per row.  THE DEFAULT for encoder backward.
+//   msda_bwd_det<T>             any dtype / shape, opt-in (tf_msda_backward_det_*): no float atomics -- contributions stored,
+//                               radix-sorted by destination row and summed in a fixed order (msda_bwd_det.h); bitwise reproducible.
 // Removed in round 4 (superseded, no default route reached them; measurements in DESIGN.md section 4.1):
 // msda_fwd_f32_win (the first LDS-window kernel, 8 lanes per pair) and msda_bwd_f32_sorted (the first sorted backward).
 // Common rules: level geometry comes from the kernel arguments (host-shape entry points) or from the
@@ -2226,6 +2228,8 @@ int backward_impl(const T *value, const int64_t *shapes_host, const int64_t *sha
     return record_hip(e);
 }
 
+#include "msda_bwd_det.h"
+
 }  // namespace
 
 namespace tfm {
@@ -2250,6 +2254,7 @@ const char *tf_msda_strerror(int status)
     case TF_MSDA_ERR_SHAPE_SUM: return "sum of H_l*W_l over levels does not equal S";
     case TF_MSDA_ERR_LAUNCH: return "HIP error while enqueueing work";
     case TF_MSDA_ERR_NO_DEVICE: return "no HIP device available";
+    case TF_MSDA_ERR_WORKSPACE: return "workspace too small (see tf_msda_backward_det_workspace_bytes) or not 8-byte aligned";
     default: return "unknown tf_msda status";
     }
 }
@@ -2370,6 +2375,47 @@ int tf_msda_backward_f64_dshapes(const double *value, const int64_t *shapes_hw_d
     if (!shapes_hw_dev) return TF_MSDA_ERR_NULL_POINTER;
     return backward_impl<double>(value, nullptr, shapes_hw_dev, loc, attn, grad_out, grad_value,
                                  grad_loc, grad_attn, N, S, M, D, L, Lq, P, stream);
+}
+
+int64_t tf_msda_backward_det_workspace_bytes(int elem_bytes, int N, int S, int M, int D, int L, int Lq, int P)
+{
+    DetPlan pl;
+    const int rc = det_plan(elem_bytes, N, S, M, D, L, Lq, P, &pl);
+    return rc != TF_MSDA_OK ? (int64_t)rc : (int64_t)pl.bytes;
+}
+int tf_msda_backward_det_f32(const float *value, const int64_t *shapes_hw_host, const float *loc, const float *attn,
+                             const float *grad_out, float *grad_value, float *grad_loc, float *grad_attn, void *workspace,
+                             int64_t workspace_bytes, int N, int S, int M, int D, int L, int Lq, int P, void *stream)
+{
+    if (!shapes_hw_host) return TF_MSDA_ERR_NULL_POINTER;
+    return backward_det_impl<float>(value, shapes_hw_host, nullptr, loc, attn, grad_out, grad_value, grad_loc, grad_attn,
+                                    workspace, workspace_bytes, N, S, M, D, L, Lq, P, stream);
+}
+int tf_msda_backward_det_f64(const double *value, const int64_t *shapes_hw_host, const double *loc, const double *attn,
+                             const double *grad_out, double *grad_value, double *grad_loc, double *grad_attn, void *workspace,
+                             int64_t workspace_bytes, int N, int S, int M, int D, int L, int Lq, int P, void *stream)
+{
+    if (!shapes_hw_host) return TF_MSDA_ERR_NULL_POINTER;
+    return backward_det_impl<double>(value, shapes_hw_host, nullptr, loc, attn, grad_out, grad_value, grad_loc, grad_attn,
+                                     workspace, workspace_bytes, N, S, M, D, L, Lq, P, stream);
+}
+int tf_msda_backward_det_f32_dshapes(const float *value, const int64_t *shapes_hw_dev, const float *loc, const float *attn,
+                                     const float *grad_out, float *grad_value, float *grad_loc, float *grad_attn,
+                                     void *workspace, int64_t workspace_bytes, int N, int S, int M, int D, int L, int Lq, int P,
+                                     void *stream)
+{
+    if (!shapes_hw_dev) return TF_MSDA_ERR_NULL_POINTER;
+    return backward_det_impl<float>(value, nullptr, shapes_hw_dev, loc, attn, grad_out, grad_value, grad_loc, grad_attn,
+                                    workspace, workspace_bytes, N, S, M, D, L, Lq, P, stream);
+}
+int tf_msda_backward_det_f64_dshapes(const double *value, const int64_t *shapes_hw_dev, const double *loc, const double *attn,
+                                     const double *grad_out, double *grad_value, double *grad_loc, double *grad_attn,
+                                     void *workspace, int64_t workspace_bytes, int N, int S, int M, int D, int L, int Lq, int P,
+                                     void *stream)
+{
+    if (!shapes_hw_dev) return TF_MSDA_ERR_NULL_POINTER;
+    return backward_det_impl<double>(value, nullptr, shapes_hw_dev, loc, attn, grad_out, grad_value, grad_loc, grad_attn,
+                                     workspace, workspace_bytes, N, S, M, D, L, Lq, P, stream);
 }
 
 }  // extern "C"

@@ -10,6 +10,7 @@
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
 
+#include <cstdlib>
 #include <vector>
 
 #include "tf_msda.h"
@@ -62,6 +63,14 @@ void raise_on(int rc, const char *what)
 
 // the level shapes for the host-shape entry points: a CPU copy of a CPU tensor is free; a device tensor goes to the *_dshapes entries
 const int64_t *host_shapes(const at::Tensor &spatial_shapes) { return spatial_shapes.data_ptr<int64_t>(); }
+
+// the deterministic backward (tf_msda_backward_det_*): TF_MSDA_DETERMINISTIC = 1 / 0, else torch.use_deterministic_algorithms
+bool deterministic_backward()
+{
+    const char *e = std::getenv("TF_MSDA_DETERMINISTIC");
+    if (e && (e[0] == '0' || e[0] == '1') && e[1] == 0) return e[0] == '1';
+    return at::globalContext().deterministicAlgorithms();
+}
 
 }  // namespace
 
@@ -125,6 +134,30 @@ std::vector<at::Tensor> ms_deform_attn_backward(const at::Tensor &value, const a
     c10::hip::HIPGuardMasqueradingAsCUDA guard(value.device());
     void *stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
     const int64_t *shp = spatial_shapes.data_ptr<int64_t>();
+    if (deterministic_backward()) {   // same signature; the workspace comes from torch's allocator
+        const int64_t bytes = tf_msda_backward_det_workspace_bytes(f32 ? 4 : 8, d.N, d.S, d.M, d.D, d.L, d.Lq, d.P);
+        if (bytes < 0) raise_on((int)bytes, "ms_deform_attn_backward (deterministic)");
+        at::Tensor ws = at::empty({bytes}, value.options().dtype(at::kByte));
+        if (spatial_shapes.is_cuda())
+            rc = f32 ? tf_msda_backward_det_f32_dshapes(value.data_ptr<float>(), shp, sampling_loc.data_ptr<float>(),
+                                                        attn_weight.data_ptr<float>(), go.data_ptr<float>(), gv.data_ptr<float>(),
+                                                        gl.data_ptr<float>(), ga.data_ptr<float>(), ws.data_ptr(), bytes, d.N, d.S, d.M, d.D,
+                                                        d.L, d.Lq, d.P, stream)
+                     : tf_msda_backward_det_f64_dshapes(value.data_ptr<double>(), shp, sampling_loc.data_ptr<double>(),
+                                                        attn_weight.data_ptr<double>(), go.data_ptr<double>(), gv.data_ptr<double>(),
+                                                        gl.data_ptr<double>(), ga.data_ptr<double>(), ws.data_ptr(), bytes, d.N, d.S, d.M,
+                                                        d.D, d.L, d.Lq, d.P, stream);
+        else
+            rc = f32 ? tf_msda_backward_det_f32(value.data_ptr<float>(), shp, sampling_loc.data_ptr<float>(), attn_weight.data_ptr<float>(),
+                                                go.data_ptr<float>(), gv.data_ptr<float>(), gl.data_ptr<float>(), ga.data_ptr<float>(),
+                                                ws.data_ptr(), bytes, d.N, d.S, d.M, d.D, d.L, d.Lq, d.P, stream)
+                     : tf_msda_backward_det_f64(value.data_ptr<double>(), shp, sampling_loc.data_ptr<double>(),
+                                                attn_weight.data_ptr<double>(), go.data_ptr<double>(), gv.data_ptr<double>(),
+                                                gl.data_ptr<double>(), ga.data_ptr<double>(), ws.data_ptr(), bytes, d.N, d.S, d.M, d.D, d.L,
+                                                d.Lq, d.P, stream);
+        raise_on(rc, "ms_deform_attn_backward (deterministic)");
+        return {gv, gl, ga};
+    }
     if (spatial_shapes.is_cuda())
         rc = f32 ? tf_msda_backward_f32_dshapes(value.data_ptr<float>(), shp, sampling_loc.data_ptr<float>(), attn_weight.data_ptr<float>(),
                                                 go.data_ptr<float>(), gv.data_ptr<float>(), gl.data_ptr<float>(), ga.data_ptr<float>(), d.N, d.S,

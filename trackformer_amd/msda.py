@@ -124,6 +124,32 @@ def last_kernel():
     return _cabi.lib().tf_msda_last_kernel().decode()
 
 
+_deterministic_backward = None   # set_deterministic_backward: True / False, None = follow the environment / torch
+
+
+def set_deterministic_backward(flag):
+    """True / False: device-tensor backward calls use (do not use) the bitwise-reproducible kernels (tf_msda_backward_det_*,
+    include/tf_msda.h) whatever the environment and torch say; None: follow them again.  Returns the previous setting."""
+    global _deterministic_backward
+    prev = _deterministic_backward
+    _deterministic_backward = None if flag is None else bool(flag)
+    return prev
+
+
+def deterministic_backward_enabled(deterministic=None):
+    """Whether a backward call with `deterministic=` this argument runs the deterministic kernels: the argument, else
+    set_deterministic_backward, else the environment variable TF_MSDA_DETERMINISTIC (1 / 0), else
+    torch.are_deterministic_algorithms_enabled().  Read at every call (MSDeformAttnFunction: at backward time)."""
+    if deterministic is not None:
+        return bool(deterministic)
+    if _deterministic_backward is not None:
+        return _deterministic_backward
+    env = _os.environ.get("TF_MSDA_DETERMINISTIC", "")
+    if env in ("0", "1"):
+        return env == "1"
+    return bool(torch.are_deterministic_algorithms_enabled())
+
+
 def ms_deform_attn_forward(value, spatial_shapes, sampling_loc, attn_weight, im2col_step=64):
     """value[N,S,M,D], spatial_shapes[L,2] i64, sampling_loc[N,Lq,M,L,P,2], attn_weight[N,Lq,M,L,P]
     -> output[N,Lq,M*D].   Same contract as the reference's MSDA.ms_deform_attn_forward
@@ -156,9 +182,12 @@ def ms_deform_attn_forward(value, spatial_shapes, sampling_loc, attn_weight, im2
 
 
 def ms_deform_attn_backward(value, spatial_shapes, sampling_loc, attn_weight, grad_output,
-                            im2col_step=64):
+                            im2col_step=64, deterministic=None):
     """-> [grad_value, grad_sampling_loc, grad_attn_weight], shaped like the respective inputs
-    (reference: src/cuda/ms_deform_attn_cuda.cu:89-168)."""
+    (reference: src/cuda/ms_deform_attn_cuda.cu:89-168).
+    deterministic (device tensors; see deterministic_backward_enabled for None): the three gradients are bit-identical from
+    call to call, on any stream, in a captured graph and for every batch size (no float atomics; slower, and it takes a
+    workspace from torch's allocator).  Host tensors: accepted and ignored, that path is deterministic already."""
     N, S, M, D, L, Lq, P = _check_inputs(value, spatial_shapes, sampling_loc, attn_weight,
                                          im2col_step)
     suf = _suffix(value.dtype)
@@ -183,10 +212,20 @@ def ms_deform_attn_backward(value, spatial_shapes, sampling_loc, attn_weight, gr
         grad_attn = torch.empty_like(attn_weight)
         tail, shp, keep = _shape_args(spatial_shapes, value)
         stream = torch.cuda.current_stream().cuda_stream
-        rc = getattr(lib, "tf_msda_backward_%s%s" % (suf, tail))(
-            value.data_ptr(), shp, sampling_loc.data_ptr(), attn_weight.data_ptr(),
-            grad_output.data_ptr(), grad_value.data_ptr(), grad_loc.data_ptr(),
-            grad_attn.data_ptr(), N, S, M, D, L, Lq, P, stream)
+        if deterministic_backward_enabled(deterministic):
+            nbytes = lib.tf_msda_backward_det_workspace_bytes(value.element_size(), N, S, M, D, L, Lq, P)
+            if nbytes < 0:
+                _cabi.check(int(nbytes), "ms_deform_attn_backward (deterministic)")
+            workspace = torch.empty(int(nbytes), dtype=torch.uint8, device=value.device)
+            rc = getattr(lib, "tf_msda_backward_det_%s%s" % (suf, tail))(
+                value.data_ptr(), shp, sampling_loc.data_ptr(), attn_weight.data_ptr(),
+                grad_output.data_ptr(), grad_value.data_ptr(), grad_loc.data_ptr(),
+                grad_attn.data_ptr(), workspace.data_ptr(), int(nbytes), N, S, M, D, L, Lq, P, stream)
+        else:
+            rc = getattr(lib, "tf_msda_backward_%s%s" % (suf, tail))(
+                value.data_ptr(), shp, sampling_loc.data_ptr(), attn_weight.data_ptr(),
+                grad_output.data_ptr(), grad_value.data_ptr(), grad_loc.data_ptr(),
+                grad_attn.data_ptr(), N, S, M, D, L, Lq, P, stream)
     del keep
     _cabi.check(rc, "ms_deform_attn_backward")
     return [grad_value, grad_loc, grad_attn]
