@@ -270,6 +270,56 @@ int tf_linear_packed_f32(const float *x, const void *w_packed, const float *bias
                          int N, int relu, int terms, void *stream);
 
 /*
+ * THE BACKWARD OF A LINEAR  y[M, N] = x[M, K] . w[N, K]^T + b[N]  as split products (trackformer_amd/csrc/linear_bwd.h; reference: the
+ * autograd of the nn.Linear layers of models/deformable_transformer.py / models/ops/modules/ms_deform_attn.py, fp32):
+ *     dx[M, K] = dy[M, N] . w[N, K]            db[N] = sum_m dy[m, n]            dw[N, K] = sum_m dy[m, n] x[m, k]
+ * Scaling.  The forward's fp16 scheme (terms = 16) is cut for O(1) activations: a fixed 2^-4, |x| < 1.0e6.  Gradients have no such
+ * range, so the operands of a backward product get powers of two per call, found on the device from their largest magnitudes and
+ * written to device memory (no host synchronisation):
+ *     role 0 (the operand split as the ACTIVATION: dy): scale2 = {s, 1 / s}; s puts amax|a| of the MATRIX into [2^14, 2^15) -- after the
+ *            scheme's 2^-4 the hi piece stays below 2^11.  (One scale: the columns of dy are the contraction of the input gradient.)
+ *     role 1 (the operand split as the WEIGHT: x):      scale2 = t[C] | 1 / t[C] (2 C floats, 16-byte aligned); t_c puts the largest
+ *            magnitude of COLUMN c into [2^13, 2^14): column k of x is output channel k of dw, what t_n is per output channel in the
+ *            forward (a column of fp32 subnormals keeps its bits).
+ * A scale depends on the exponent of its amax alone (a -> 2^k a gives s -> 2^-k s exactly; every result below is scale-equivariant bit
+ * for bit while nothing leaves fp32's range); it is 1 for an all-zero matrix / column and for one that holds a NaN or an inf; 1 always under
+ * terms = 6 (bf16 pieces have fp32's exponent range).  The operand is multiplied by s as it is staged, the result by the inverse
+ * in the epilogue: both exact.  An element below 2^-25 of its matrix's amax is held to an absolute 2^-32 / s (THE SPLIT PRODUCT).
+ * No atomics anywhere: sums over rows are two-stage reductions in a fixed order, so every result is a pure function of the
+ * arguments -- bit-identical from call to call, on any stream and in a captured HIP graph.
+ * Non-finite operands: an output whose exact value is NaN or +-inf is non-finite.  Nothing is promised about which OTHER outputs stay
+ * finite (a non-finite amax switches the scaling off).
+ *
+ *   tf_linear_grad_stats_f32     one pass over a[M, C]: scale2 for `role` (0 / 1), and, if colsum != NULL, colsum[c] = sum_m a[m, c]
+ *                                (the bias gradient when a = dy), summed in a fixed order.  C % 4 == 0, a / scale2 / colsum 16-byte
+ *                                aligned.  workspace: tf_linear_grad_stats_workspace_bytes(M, C, role, colsum != NULL) bytes, 16-byte
+ *                                aligned (4 bytes per row block, rounded up to 16, + a row of C floats per row block with colsum, + one
+ *                                more for role 1; row blocks: ceil(M / 64) up to 32 768 rows, 512 beyond).
+ *   tf_linear_wgrad_split_f32    dw from dy (role 0, scale dy_scale2) and x (role 1, scale x_scale2); fp16 scheme: the epilogue
+ *                                multiplies dw[n, k] by 16 / (s t_k).  The row loop is cut into `msplit` chunks that run as separate workgroups
+ *                                and write partial sums to `workspace`; a second launch adds them in the order 0, 1, ...  msplit is a
+ *                                function of (M, K, N) only (tf_msda_set_option("wgrad_msplit", n) forces it; 0: per shape);
+ *                                tf_linear_wgrad_workspace_bytes(M, K, N) = msplit N K 4 bytes (0 for msplit == 1: workspace may be
+ *                                NULL), 16-byte aligned.  K % 4 == 0, N % 4 == 0, 16-byte aligned dy / x / dw, dy / x / dw below
+ *                                3 GiB each, else TF_MSDA_ERR_BAD_DIMS.  Rows at or beyond M are never read.
+ *   tf_linear_dgrad_packed_f32   dx = dy . w: tf_linear_packed_f32 with dy as the activation and wt_packed =
+ *                                tf_linear_pack_weight_f32(w^T [K, N] row-major, K = N, N = K, terms); dy is multiplied by s as it
+ *                                is staged and the result by 1 / s: bit-identical to (1 / s) . tf_linear_packed_f32(s dy, wt_packed).
+ *                                dy_scale2 may be NULL (no scaling).  N % 64 == 0, 16-byte aligned dy / wt_packed, dx below 3 GiB.
+ * Checked in this order, before any GPU work: NULL pointer -> TF_MSDA_ERR_NULL_POINTER, dimensions / alignment -> TF_MSDA_ERR_BAD_DIMS,
+ * workspace too small or misaligned -> TF_MSDA_ERR_WORKSPACE.  The *_workspace_bytes functions return -1 for dimensions the entry
+ * point rejects.
+ */
+int64_t tf_linear_grad_stats_workspace_bytes(int64_t M, int C, int role, int with_colsum);
+int tf_linear_grad_stats_f32(const float *a, float *scale2, float *colsum, void *workspace, int64_t workspace_bytes, int64_t M, int C,
+                             int role, int terms, void *stream);
+int64_t tf_linear_wgrad_workspace_bytes(int64_t M, int K, int N);
+int tf_linear_wgrad_split_f32(const float *dy, const float *x, const float *dy_scale2, const float *x_scale2, float *dw, void *workspace,
+                              int64_t workspace_bytes, int64_t M, int K, int N, int terms, void *stream);
+int tf_linear_dgrad_packed_f32(const float *dy, const float *dy_scale2, const void *wt_packed, float *dx, int64_t M, int K, int N,
+                               int terms, void *stream);
+
+/*
  * Convolution of a channels_last activation through the same kernel (an implicit GEMM over the output pixels; the weight
  * fragments streamed from L2, only the shifted input pixels pass LDS): ks = 3 (padding 1) or 1 (no padding), stride 1 or 2.
  *   x [nimg, hin, win, cin] NHWC fp32, below 3 GiB;  y [nimg, hout, wout, cout] NHWC, below 3 GiB;  cin % 64 == 0

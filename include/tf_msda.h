@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define TF_MSDA_ABI_VERSION 4
+#define TF_MSDA_ABI_VERSION 5
 #define TF_MSDA_MAX_LEVELS 16
 
 typedef enum tf_msda_status {
@@ -55,7 +55,7 @@ typedef enum tf_msda_status {
     TF_MSDA_ERR_SHAPE_SUM = -3,     /* sum_l H_l*W_l != S (host-shape entry points only) */
     TF_MSDA_ERR_LAUNCH = -4,        /* HIP reported an error enqueueing work (see tf_msda_last_hip_error) */
     TF_MSDA_ERR_NO_DEVICE = -5,     /* no HIP device available */
-    TF_MSDA_ERR_WORKSPACE = -6      /* caller's workspace smaller than tf_msda_backward_det_workspace_bytes, or misaligned */
+    TF_MSDA_ERR_WORKSPACE = -6      /* caller's workspace smaller than the entry point's *_workspace_bytes, or misaligned */
 } tf_msda_status;
 
 /* ABI version of the loaded library (== TF_MSDA_ABI_VERSION it was built with). */
@@ -98,6 +98,8 @@ int tf_msda_set_tiled(int mode);
  *   "direct9"       1 / 0: msda_fwd_f32_direct9 for D == 36 decoder calls (off: msda_fwd_f32_buf)
  *   "ffn_ti" "linln_ti" "linear_stream_ti"   row tiles per block of tf_ffn_fused_f32 / tf_linear_res_ln_f32 /
  *                   tf_linear_packed_f32 (include/tf_fused.h; 0 = per shape)
+ *   "wgrad_msplit"  chunks the row loop of tf_linear_wgrad_split_f32 is cut into (1..64; 0 = per shape, the default).  Unlike the
+ *                   other knobs it changes the summation order of dw -- and the workspace tf_linear_wgrad_workspace_bytes asks for
  * Knobs of experiments that were measured and removed (linear_variant, linear_bufstore, linear_deep, linear_astat,
  * conv3_bufload, bwd_sorted2, tiled = 1) are unknown names now.
  */

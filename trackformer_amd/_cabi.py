@@ -59,6 +59,11 @@ EXPORTED_SYMBOLS = (
     "tf_linear_packed_bytes",
     "tf_linear_pack_weight_f32",
     "tf_linear_packed_f32",
+    "tf_linear_grad_stats_workspace_bytes",
+    "tf_linear_grad_stats_f32",
+    "tf_linear_wgrad_workspace_bytes",
+    "tf_linear_wgrad_split_f32",
+    "tf_linear_dgrad_packed_f32",
     "tf_linear_split_add_f32",
     "tf_ffn_fused_f32",
     "tf_linear_res_ln_f32",
@@ -67,7 +72,7 @@ EXPORTED_SYMBOLS = (
     "tf_nms_host_f32",
 )
 
-ABI_VERSION = 4   # 4: tf_msda_backward_det_* and TF_MSDA_ERR_WORKSPACE (3: the split-product entry points take w_lo / w_scale / terms)
+ABI_VERSION = 5   # 5: tf_linear_grad_stats / wgrad / dgrad (4: tf_msda_backward_det_* and TF_MSDA_ERR_WORKSPACE; 3: the split-product entry points take w_lo / w_scale / terms)
 
 _lib = None
 
@@ -177,6 +182,17 @@ def lib():
     L.tf_linear_split_add_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_int64, ci, ci, vp]
     L.tf_linear_packed_f32.restype = ci
     L.tf_linear_packed_f32.argtypes = [vp, vp, vp, vp, vp, ctypes.c_int64, ci, ci, ci, ci, vp]
+    i64 = ctypes.c_int64
+    L.tf_linear_grad_stats_workspace_bytes.restype = i64
+    L.tf_linear_grad_stats_workspace_bytes.argtypes = [i64, ci, ci, ci]
+    L.tf_linear_grad_stats_f32.restype = ci
+    L.tf_linear_grad_stats_f32.argtypes = [vp, vp, vp, vp, i64, i64, ci, ci, ci, vp]
+    L.tf_linear_wgrad_workspace_bytes.restype = i64
+    L.tf_linear_wgrad_workspace_bytes.argtypes = [i64, ci, ci]
+    L.tf_linear_wgrad_split_f32.restype = ci
+    L.tf_linear_wgrad_split_f32.argtypes = [vp, vp, vp, vp, vp, vp, i64, i64, ci, ci, ci, vp]
+    L.tf_linear_dgrad_packed_f32.restype = ci
+    L.tf_linear_dgrad_packed_f32.argtypes = [vp, vp, vp, vp, i64, ci, ci, ci, vp]
     L.tf_conv_packed_f32.restype = ci
     L.tf_conv_packed_f32.argtypes = [vp, vp, vp, vp, vp, vp] + [ci] * 10 + [vp]
     L.tf_mha_core_f32.restype = ci

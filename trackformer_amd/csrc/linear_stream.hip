@@ -180,7 +180,10 @@ struct WFrags {
 
 constexpr int stream_min_waves(int ti, int tj, int wc) { return (4 / wc) * ti * tj <= 6 && ti <= 3 ? 2 : 1; }   // blocks per CU the register budget is cut for
 
-template <int SP, int TI, int TJ, int WC, bool CONV>
+// XSC (the input gradient of a linear, tf_linear_dgrad_packed_f32 in linear_bwd.h; off in every other instantiation): `bias` carries
+// scale2 = {s, 1 / s} (device memory, powers of two) instead of a bias: the activation is multiplied by s as it is staged and the
+// result by 1 / s in the epilogue -- both exact, so the call equals (1 / s) . tf_linear_packed_f32(s x) bit for bit.
+template <int SP, int TI, int TJ, int WC, bool CONV, bool XSC = false>
 __global__ void __launch_bounds__(kThreads, (stream_min_waves(TI, TJ, WC)))
 stream_gemm_kernel(const float *__restrict__ X, const u32x4 *__restrict__ Wp, const float *__restrict__ bias, const float *R,
                    float *Y, int M, int K, int N, int mblocks, int nblocks, int relu, int kslices, const StreamConv cv)
@@ -203,6 +206,11 @@ stream_gemm_kernel(const float *__restrict__ X, const u32x4 *__restrict__ Wp, co
     const int sbeg = kslices > 0 ? (int)blockIdx.y * kslices : 0;
     const int send = kslices > 0 ? min(K / kSlice, sbeg + kslices) : K / kSlice;   // this block's slices: [sbeg, send), an even number
     if (kslices > 0) Y += (size_t)blockIdx.y * M * N;
+    float xsc = 1.f, xinv = 1.f;
+    if constexpr (XSC) {
+        xsc = bias[0];
+        xinv = bias[1];
+    }
 
     f32x16 acc[TI][TJ];
 #pragma unroll
@@ -282,7 +290,8 @@ stream_gemm_kernel(const float *__restrict__ X, const u32x4 *__restrict__ Wp, co
 #pragma unroll
             for (int p = 0; p < NA; ++p) pc[p] = u32x2{__builtin_bit_cast(unsigned, src[it].x) + (unsigned)p, __builtin_bit_cast(unsigned, src[it].z)};
 #else
-            split4<SP>(src[it], pc);
+            if constexpr (XSC) split4<SP>(src[it] * xsc, pc);
+            else split4<SP>(src[it], pc);
 #endif
             const int o = (it * 32 + arow) * kStride + ac4 * 4;
 #pragma unroll
@@ -400,7 +409,7 @@ stream_gemm_kernel(const float *__restrict__ X, const u32x4 *__restrict__ Wp, co
     for (int j = 0; j < TJ; ++j) {
         const int col = n0 + (wc * TJ + j) * 32 + (lane & 31);
         const bool colok = col < N;
-        const float b = (bias && colok) ? bias[col] : 0.f;
+        const float b = (!XSC && bias && colok) ? bias[col] : 0.f;
         float rsc = 1.f;   // fp16 scheme: the output channel's power of two (behind the fragments of the packed weight)
         if constexpr (Split<SP>::F16) rsc = reinterpret_cast<const float *>(Wp + (size_t)((N + kBN - 1) / kBN * (kBN / 32)) * KQ * NB * 64)[colok ? col : 0];
 #pragma unroll
@@ -418,6 +427,7 @@ stream_gemm_kernel(const float *__restrict__ X, const u32x4 *__restrict__ Wp, co
                 float v = Split<SP>::F16 ? __builtin_fmaf(acc[i][j][e], rsc, b) : acc[i][j][e] + b;
                 if (R != nullptr) v += rv[e];
                 if (relu) v = v < 0.f ? 0.f : v;
+                if constexpr (XSC) v *= xinv;
                 __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), yrs, base + (unsigned)(((e & 3) + 8 * (e >> 2)) * N) * 4u, 0, tfm::kStoreAux);
             }
         }
@@ -976,7 +986,7 @@ struct StreamCall {
     int ksplit;         // pieces the K loop is cut into (1: none)
 };
 
-template <int SP, int TI, int TJ, int WC, bool CONV>
+template <int SP, int TI, int TJ, int WC, bool CONV, bool XSC = false>
 int launch_stream(const StreamCall &c, hipStream_t s)
 {
     constexpr int BM = (4 / WC) * TI * 32, BN = WC * TJ * 32;
@@ -992,7 +1002,7 @@ int launch_stream(const StreamCall &c, hipStream_t s)
     if (gx > 0x7fffffffLL || gz > 65535) return TF_MSDA_ERR_BAD_DIMS;
     const bool partial = gz > 1;
     float *out = partial ? c.workspace : c.y;
-    hipLaunchKernelGGL((stream_gemm_kernel<SP, TI, TJ, WC, CONV>), dim3((unsigned)gx, (unsigned)gz), dim3(kThreads), 0, s, c.x, c.wp,
+    hipLaunchKernelGGL((stream_gemm_kernel<SP, TI, TJ, WC, CONV, XSC>), dim3((unsigned)gx, (unsigned)gz), dim3(kThreads), 0, s, c.x, c.wp,
                        partial ? nullptr : c.bias, partial ? nullptr : c.res, out, c.M, c.K, c.N, mblocks, nblocks, partial ? 0 : c.relu,
                        kslices, c.cv);
     if (hipGetLastError() != hipSuccess) return TF_MSDA_ERR_LAUNCH;
@@ -1304,3 +1314,6 @@ extern "C" int tf_conv_packed_f32(const float *x, const void *w_packed, const fl
         return sp == 3 ? halo_dispatch<3>(c, static_cast<hipStream_t>(stream)) : halo_dispatch<16>(c, static_cast<hipStream_t>(stream));
     return stream_dispatch_scheme<true>(sp, c, static_cast<hipStream_t>(stream));
 }
+
+// the backward of a linear (statistics, weight gradient, input gradient): kernels and entry points
+#include "linear_bwd.h"

@@ -75,6 +75,8 @@ int linear_stream_set_ti(int v);
 int conv_halo_set(int v);
 // linear_stream.hip: the LDS-DMA GEMM behind tf_linear_packed_f32: 0 = off (the stream form), 1..4 = a fixed block shape, 9 = per call
 int linear_dma_set(int v);
+// linear_stream.hip (linear_bwd.h): chunks the row loop of tf_linear_wgrad_split_f32 is cut into (1..64; 0 = per shape); returns the previous value
+int wgrad_msplit_set(int v);
 // mha_core.hip: 1 = the matrix-core kernel (default), 0 = the vector kernel of round 4; returns the previous value
 int mha_set_mfma(int v);
 

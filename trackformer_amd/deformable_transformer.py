@@ -39,6 +39,10 @@ def _ffn_hidden(linear, activation, x, inference):
         x2 = x.reshape(-1, x.shape[-1])
         y = torch._addmm_activation(linear.bias, x2, linear.weight.t(), use_gelu=False)
         return y.view(*x.shape[:-1], y.shape[-1])
+    if not inference and activation is F.relu and fused.train_route(x):   # opt-in: the split product with its own backward
+        y = fused.linear_train(x, linear.weight, linear.bias, relu=True)
+        if y is not None:
+            return y
     return activation(linear(x))
 
 

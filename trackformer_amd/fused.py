@@ -1050,9 +1050,14 @@ def postprocess_pack(logits, boxes, img_h, img_w, clip):
 
 
 def module_linear(module, x, inference):
-    """module(x) for an nn.Linear: the split product on the GPU inference path when enabled, else the module."""
+    """module(x) for an nn.Linear: the split product on the GPU inference path when enabled, else the module (with gradients enabled and
+    set_split_linear_training(True): the split product with its own backward, linear_train)."""
     if inference and _split_linear:
         y = linear(x, module.weight, module.bias)
+        if y is not None:
+            return y
+    elif not inference and train_route(x):
+        y = linear_train(x, module.weight, module.bias)
         if y is not None:
             return y
     return module(x)
@@ -1242,3 +1247,181 @@ ffn = _ranged("ffn", lambda x, linear1, linear2, *a, **k: (linear1.weight, linea
 linear_residual_norm = _ranged("linear_residual_norm", lambda x, linear, *a, **k: (linear.weight,), lambda x, *a, **k: (x,))(linear_residual_norm)
 stem_conv = _ranged("stem_conv", lambda x, weight, *a, **k: (weight,), lambda x, *a, **k: (x,))(stem_conv)
 conv3x3 = _ranged("conv3x3", lambda x, w_taps, *a, **k: (w_taps,), lambda x, *a, **k: (x,))(conv3x3)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# THE TRAINING PATH OF THE LINEARS (opt-in; include/tf_fused.h: THE BACKWARD OF A LINEAR; csrc/linear_bwd.h).  With gradients
+# enabled every nn.Linear of the encoder / decoder runs on the fp32 library, forward and backward.  set_split_linear_training(True) /
+# TF_SPLIT_LINEAR_TRAIN=1 routes module_linear, the feed-forward block's first linear and the four projections of MSDeformAttn through
+# linear_train instead: the forward is linear() (bit-identical to the inference path), the backward the library's own input-gradient,
+# weight-gradient and bias-gradient kernels -- no float atomics, bit-identical from call to call.  NOT covered: convolutions,
+# nn.MultiheadAttention's internals, LayerNorm.  OFF by default: whether it is faster inside a training step is a measurement
+# (tools/bench_linear_backward.py, profiles/linear_backward_bench.json), not a promise.
+_split_linear_train = None    # None: follow TF_SPLIT_LINEAR_TRAIN (unset: off)
+_train_counts = {"dgrad_own": 0, "dgrad_torch": 0, "wgrad_own": 0, "wgrad_torch": 0, "bias_own": 0, "bias_torch": 0}
+
+
+def split_linear_training_enabled():
+    if _split_linear_train is not None:
+        return _split_linear_train
+    return os.environ.get("TF_SPLIT_LINEAR_TRAIN", "0") not in ("", "0")
+
+
+def set_split_linear_training(flag):
+    """Switch the split-product training path of the linears on or off (process-wide; None: follow TF_SPLIT_LINEAR_TRAIN again);
+    returns the previous setting."""
+    global _split_linear_train
+    prev = split_linear_training_enabled()
+    _split_linear_train = None if flag is None else bool(flag)
+    return prev
+
+
+def train_route(x):
+    """A call with gradients enabled that linear_train takes: the switch is on and x is an fp32 tensor on the device."""
+    return split_linear_training_enabled() and torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.float32
+
+
+def train_route_counts(reset=False):
+    """How many input / weight / bias gradients of linear_train went to the library's own kernels and how many to torch."""
+    out = dict(_train_counts)
+    if reset:
+        for k in _train_counts:
+            _train_counts[k] = 0
+    return out
+
+
+class _NotApplicable(Exception):
+    pass
+
+
+def _packed_weight_t(weight, terms):
+    """Fragment-order image of weight^T (the `weight` of the input gradient dx = dy . w), cached on the parameter with its version
+    counter like _packed_weight; None when it cannot be built (shape; stream capture without a cached image)."""
+    cache = getattr(weight, "_tf_packed_t", None)
+    if cache is None or cache[0] != weight._version:
+        cache = (weight._version, {})
+        weight._tf_packed_t = cache
+    capturing = torch.cuda.is_current_stream_capturing()
+    hit = cache[1].get(terms)
+    if hit is None:
+        if capturing:
+            return None   # never build a cached buffer inside a graph's memory pool
+        N, K = weight.shape
+        nbytes = _cabi.lib().tf_linear_packed_bytes(N, K, terms)
+        if nbytes <= 0:
+            return None
+        with torch.cuda.device(weight.device):
+            wt = weight.detach().t().contiguous()
+            buf = torch.empty(nbytes, dtype=torch.uint8, device=weight.device)
+            rc = _cabi.lib().tf_linear_pack_weight_f32(wt.data_ptr(), buf.data_ptr(), N, K, terms, _stream(weight.device))
+        _cabi.check(rc, "tf_linear_pack_weight_f32")
+        hit = (buf, torch.cuda.current_stream(weight.device))
+        cache[1][terms] = hit
+    elif not capturing and hit[1] != torch.cuda.current_stream(weight.device):
+        # built on another stream (a training step rebuilds it for the stream that runs the backward: no host synchronisation)
+        torch.cuda.current_stream(weight.device).wait_stream(hit[1])
+    return hit[0]
+
+
+def _grad_stats(a, role, terms, colsum):
+    """tf_linear_grad_stats_f32 of a [M, C] -> (scale2: {s, 1 / s} for role 0, t[C] | 1 / t[C] for role 1; colsum [C] or None), on the
+    device."""
+    L = _cabi.lib()
+    M, C = a.shape
+    nbytes = L.tf_linear_grad_stats_workspace_bytes(M, C, role, 1 if colsum else 0)
+    if nbytes < 0:
+        _cabi.check(-2, "tf_linear_grad_stats_f32")
+    ws = torch.empty(int(nbytes), dtype=torch.uint8, device=a.device)
+    scale2 = torch.empty(2 if role == 0 else 2 * C, dtype=torch.float32, device=a.device)
+    cs = torch.empty(C, dtype=torch.float32, device=a.device) if colsum else None
+    rc = L.tf_linear_grad_stats_f32(a.data_ptr(), scale2.data_ptr(), _ptr(cs), ws.data_ptr(), int(nbytes), M, C, role, terms,
+                                    _stream(a.device))
+    _cabi.check(rc, "tf_linear_grad_stats_f32")
+    return scale2, cs
+
+
+class _LinearTrain(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, relu):
+        with one_stream():   # a training step: the weight images are rebuilt every step for the stream that uses them next
+            y = linear(x, weight, bias, relu=relu)
+        if y is None:
+            # linear() declined.  For a SHAPE reason (K % 32) on tensors it would otherwise take, the forward is torch's and the backward
+            # below still runs (own kernels where they take the shape, torch where not); any other reason: not this function's call
+            if not (_split_linear and x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and weight.dim() == 2
+                    and weight.device == x.device and x.shape[-1] == weight.shape[1] and x.numel() > 0
+                    and (bias is None or (bias.dtype == torch.float32 and bias.device == x.device))):
+                raise _NotApplicable()
+            y = F.linear(x, weight, bias)
+            if relu:
+                y = torch.relu(y)
+        ctx.relu = relu
+        ctx.terms = 6 if (_split_terms == 16 and _routed(weight)) else _split_terms
+        ctx.save_for_backward(x, weight, y if relu else None)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, weight, y = ctx.saved_tensors
+        need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        N, K = weight.shape
+        terms = ctx.terms
+        dy2 = dy.reshape(-1, N)
+        if ctx.relu:
+            dy2 = torch.ops.aten.threshold_backward(dy2, y.reshape(-1, N), 0.0)
+        x2 = x.reshape(-1, K)
+        dy2 = dy2 if dy2.is_contiguous() and not dy2.data_ptr() & 15 else dy2.clone(memory_format=torch.contiguous_format)
+        x2 = x2 if x2.is_contiguous() and not x2.data_ptr() & 15 else x2.clone(memory_format=torch.contiguous_format)
+        M = dy2.shape[0]
+        L = _cabi.lib()
+        own = K % 4 == 0 and N % 4 == 0 and max(M * N, M * K, N * K) * 4 < 0xC0000000 and dy2.dtype == torch.float32
+        dx = dw = db = None
+        with torch.cuda.device(dy2.device), one_stream():
+            stream = _stream(dy2.device)
+            s_dy = s_x = None
+            if own and (need_x or need_w or need_b):
+                s_dy, db = _grad_stats(dy2, 0, terms, need_b)
+            if need_b:
+                _train_counts["bias_own" if db is not None else "bias_torch"] += 1
+                if db is None:
+                    db = dy2.sum(0)
+            if need_x:
+                packed_t = _packed_weight_t(weight, terms) if own and N % 64 == 0 and (M + 256) * K * 4 < 0xC0000000 else None
+                if packed_t is not None:
+                    dx = torch.empty((M, K), dtype=torch.float32, device=dy2.device)
+                    rc = L.tf_linear_dgrad_packed_f32(dy2.data_ptr(), s_dy.data_ptr(), packed_t.data_ptr(), dx.data_ptr(), M, K, N, terms, stream)
+                    _cabi.check(rc, "tf_linear_dgrad_packed_f32")
+                    _train_counts["dgrad_own"] += 1
+                else:
+                    dx = dy2 @ weight.detach()
+                    _train_counts["dgrad_torch"] += 1
+                dx = dx.view(x.shape)
+            if need_w:
+                if own:
+                    s_x, _ = _grad_stats(x2, 1, terms, False)
+                    nbytes = int(L.tf_linear_wgrad_workspace_bytes(M, K, N))
+                    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dy2.device)
+                    dw = torch.empty((N, K), dtype=torch.float32, device=dy2.device)
+                    rc = L.tf_linear_wgrad_split_f32(dy2.data_ptr(), x2.data_ptr(), s_dy.data_ptr(), s_x.data_ptr(), dw.data_ptr(),
+                                                     ws.data_ptr(), nbytes, M, K, N, terms, stream)
+                    _cabi.check(rc, "tf_linear_wgrad_split_f32")
+                    _train_counts["wgrad_own"] += 1
+                else:
+                    dw = dy2.t() @ x2
+                    _train_counts["wgrad_torch"] += 1
+        return dx, dw, db, None
+
+
+def linear_train(x, weight, bias=None, relu=False):
+    """act(x @ weight^T + bias) with the library's own backward: the forward IS linear() (bit-identical to the inference path; None
+    where linear() declines the tensors -- host tensors, another dtype, split linears switched off: the caller keeps module(x); a
+    shape linear() does not take, K % 32 != 0, is computed by torch inside so that the function never fails for a shape reason), the
+    backward runs tf_linear_grad_stats_f32 on dy (with the bias
+    gradient) and on x, tf_linear_dgrad_packed_f32 and tf_linear_wgrad_split_f32 (include/tf_fused.h).  A gradient whose kernel does
+    not take the shape (K or N not a multiple of 4; the input gradient: N not a multiple of 64) is computed by torch inside the
+    backward: train_route_counts() tells which path ran."""
+    try:
+        return _LinearTrain.apply(x, weight, bias, relu)
+    except _NotApplicable:
+        return None

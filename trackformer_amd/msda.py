@@ -434,8 +434,8 @@ class MSDeformAttn(nn.Module):
 
         if query_pos is not None:
             query = query + query_pos
-        sampling_offsets = self.sampling_offsets(query).view(N, Len_q, M, L, P, 2)
-        attention_weights = self.attention_weights(query).view(N, Len_q, M, L * P)
+        sampling_offsets = fused.module_linear(self.sampling_offsets, query, False).view(N, Len_q, M, L, P, 2)
+        attention_weights = fused.module_linear(self.attention_weights, query, False).view(N, Len_q, M, L * P)
         attention_weights = F.softmax(attention_weights, -1).view(N, Len_q, M, L, P)
         if query_attn_mask is not None:
             attention_weights = attention_weights.masked_fill(
@@ -454,4 +454,4 @@ class MSDeformAttn(nn.Module):
                              .format(reference_points.shape[-1]))
         output = MSDeformAttnFunction.apply(value, input_spatial_shapes, sampling_locations,
                                             attention_weights, self.im2col_step)
-        return self.output_proj(output)
+        return fused.module_linear(self.output_proj, output, False)
