@@ -68,7 +68,7 @@ def set_conv_split_skip(shapes):
     """shapes: iterable of (cin, cout, kernel, stride) that keep the library convolution; returns the previous set."""
     global _conv_split_skip
     prev, _conv_split_skip = _conv_split_skip, frozenset(tuple(int(v) for v in s) for s in shapes)
-    return prev
+    return fused._switched(prev, _conv_split_skip)
 
 
 def _split_route_allowed(conv):
@@ -79,14 +79,14 @@ def set_conv3x3_split(on):
     """Route the bottlenecks' 3 x 3 convolutions through the split-product kernel (process-wide); returns the previous setting."""
     global _conv3x3_split
     prev, _conv3x3_split = _conv3x3_split, bool(on)
-    return prev
+    return fused._switched(prev, _conv3x3_split)
 
 
 def set_conv1x1_split(on):
     """Route the stride-1 1 x 1 convolutions through the split-product GEMM (process-wide); returns the previous setting."""
     global _conv1x1_split
     prev, _conv1x1_split = _conv1x1_split, bool(on)
-    return prev
+    return fused._switched(prev, _conv1x1_split)
 
 
 def conv1x1_as_gemm(x, w2d, bias, residual, relu, linear_fn):
@@ -143,6 +143,7 @@ class _FoldCache:
 
     def __init__(self):
         self.key = None
+        self.srcs = None           # the source tensor OBJECTS of `key` (a replaced parameter starts again at version 0)
         self.bias = None
         self._conv = self._bn = None
         self._weight = None        # 4-d, library path
@@ -188,8 +189,8 @@ class _FoldCache:
     def get(self, conv: nn.Conv2d, bn: FrozenBatchNorm2d):
         """-> the folded shift (bias); the weight images are the properties above."""
         srcs = (conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var)
-        key = tuple((t.data_ptr(), t._version, t.device, t.dtype) for t in srcs)
-        if key != self.key:
+        key = tuple(fused.source_key(t) for t in srcs)
+        if key != self.key or not fused.same_sources(self.srcs, srcs):
             with torch.no_grad():
                 _, shift = bn.scale_shift()
                 self.bias = self._published(shift.contiguous())
@@ -199,7 +200,7 @@ class _FoldCache:
             if any(fused._routed(t) for t in (self._weight2d, self._weight_taps) if t is not None):
                 fused.route_six_terms(conv.weight)
             self._weight = self._weight2d = self._weight_taps = None
-            self.key = key
+            self.key, self.srcs = key, srcs
         return self.bias
 
 
@@ -223,7 +224,7 @@ _TRAIN_NOGRAD_LIBRARY = _os.environ.get("TF_TRAIN_FOLD", "1") == "lib"
 def set_train_fold(on: bool) -> bool:
     global _train_fold
     prev, _train_fold = _train_fold, bool(on)
-    return prev
+    return fused._switched(prev, _train_fold)
 
 
 def _frozen(module: nn.Module) -> bool:

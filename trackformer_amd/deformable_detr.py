@@ -57,34 +57,43 @@ class DeformableDETR(DETR):
         self.with_box_refine = with_box_refine
         self.two_stage = two_stage
 
-        prior_prob = 0.01
-        self.class_embed.bias.data.fill_(-math.log((1 - prior_prob) / prior_prob))
-        nn.init.constant_(self.bbox_embed.layers[-1].weight.data, 0)
-        nn.init.constant_(self.bbox_embed.layers[-1].bias.data, 0)
-        for p in self.input_proj:
-            nn.init.xavier_uniform_(p[0].weight, gain=1)
-            nn.init.constant_(p[0].bias, 0)
-
         # one head per decoder layer (+1 for the two-stage proposal head)
         num_pred = transformer.decoder.num_layers + (1 if two_stage else 0)
         if with_box_refine:
             self.class_embed = _get_clones(self.class_embed, num_pred)
             self.bbox_embed = _get_clones(self.bbox_embed, num_pred)
-            nn.init.constant_(self.bbox_embed[0].layers[-1].bias.data[2:], -2.0)
             self.transformer.decoder.bbox_embed = self.bbox_embed  # iterative refinement
         else:
-            nn.init.constant_(self.bbox_embed.layers[-1].bias.data[2:], -2.0)
             self.class_embed = nn.ModuleList([self.class_embed for _ in range(num_pred)])
             self.bbox_embed = nn.ModuleList([self.bbox_embed for _ in range(num_pred)])
             self.transformer.decoder.bbox_embed = None
         if two_stage:
             self.transformer.decoder.class_embed = self.class_embed
-            for box_embed in self.bbox_embed:
-                nn.init.constant_(box_embed.layers[-1].bias.data[2:], 0.0)
+        self._reset_parameters()   # (before the merge convolutions are created: the order of the random draws of the reference)
 
         if self.merge_frame_features:
             merge = nn.Conv2d(self.hidden_dim * 2, self.hidden_dim, kernel_size=1)
             self.merge_features = _get_clones(merge, num_feature_levels)
+
+    def _reset_parameters(self):
+        """The head and input-projection initialisation of the reference (models/deformable_detr.py:92-117), in place on the
+        parameters under no_grad -- never through `.data`, which the caches of the weight images cannot see: calling it on a
+        model that has already run is detected like any other in-place update."""
+        prior_prob = 0.01
+        with torch.no_grad():
+            for head in self.class_embed:
+                head.bias.fill_(-math.log((1 - prior_prob) / prior_prob))
+            for box_embed in self.bbox_embed:
+                nn.init.constant_(box_embed.layers[-1].weight, 0)
+                nn.init.constant_(box_embed.layers[-1].bias, 0)
+            for p in self.input_proj:
+                nn.init.xavier_uniform_(p[0].weight, gain=1)
+                nn.init.constant_(p[0].bias, 0)
+            # with box refinement the heads are clones and only the first starts from small boxes; without, they are one module
+            self.bbox_embed[0].layers[-1].bias[2:].fill_(-2.0)
+            if self.two_stage:
+                for box_embed in self.bbox_embed:
+                    box_embed.layers[-1].bias[2:].fill_(0.0)
 
     # ------------------------------------------------------------------------------------------
     def _input_proj(self, level, x):

@@ -158,8 +158,9 @@ class DeformableTransformer(nn.Module):
             if isinstance(m, MSDeformAttn):
                 m._reset_parameters()
         if not self.two_stage:
-            xavier_uniform_(self.reference_points.weight.data, gain=1.0)
-            constant_(self.reference_points.bias.data, 0.)
+            with torch.no_grad():   # (on the parameters, not through `.data`: see MSDeformAttn._reset_parameters)
+                xavier_uniform_(self.reference_points.weight, gain=1.0)
+                constant_(self.reference_points.bias, 0.)
         normal_(self.level_embed)
 
     # ------------------------------------------------------------------ two-stage helpers
@@ -213,15 +214,15 @@ class DeformableTransformer(nn.Module):
         if self.training or torch.is_grad_enabled():
             return self.reference_points(query_embed).sigmoid()
         lin = self.reference_points
-        key = (id(query_param), query_param._version, query_param.data_ptr(), lin.weight._version, lin.weight.data_ptr(),
-               lin.bias._version, bs, query_embed.device)
+        srcs = (query_param, lin.weight, lin.bias)
+        key = tuple((id(t), fused.source_key(t)) for t in srcs) + (bs, query_embed.device)
         cache = self.__dict__.setdefault("_ref_points_cache", {})
         hit = cache.get(key)
         if hit is None:
             value = lin(query_embed).sigmoid()
             if (query_embed.is_cuda and torch.cuda.is_current_stream_capturing()) or len(cache) >= _KEEP_CACHE_ENTRIES:
                 return value   # never keep a buffer of a graph's memory pool; a full cache recomputes, it never evicts
-            hit = (value, query_param)
+            hit = (value, srcs)   # (the sources are kept alive next to the result: an id() in the key cannot be reused by another tensor)
             if value.is_cuda:
                 fused._publish_barrier(value.device)   # built on this stream, read by every lane's stream
             cache[key] = hit
@@ -241,14 +242,14 @@ class DeformableTransformer(nn.Module):
         # [N, S, C] result and its inputs for ever without being hit again (~90 MB per entry at batch 2, 800 x 1333).
         if not all(getattr(p, "_tf_cached_geometry", False) for p in pos_embeds):
             return compute()
-        key = tuple((id(p), p._version) for p in pos_embeds) + (self.level_embed._version, self.level_embed.data_ptr())
+        key = tuple((id(p), p._version) for p in pos_embeds) + (id(self.level_embed), fused.source_key(self.level_embed))
         cache = self.__dict__.setdefault("_lvl_pos_cache", {})
         hit = cache.get(key)
         if hit is None:
             if (pos_embeds[0].is_cuda and torch.cuda.is_current_stream_capturing()) or len(cache) >= _KEEP_CACHE_ENTRIES:
                 return compute()   # never keep a buffer of a graph's memory pool; a full cache recomputes, it never evicts
             # the inputs are kept alive next to the result: an id() in the key can then not be reused by another tensor
-            hit = (compute(), list(pos_embeds))
+            hit = (compute(), list(pos_embeds) + [self.level_embed])
             if pos_embeds[0].is_cuda:
                 fused._publish_barrier(pos_embeds[0].device)   # built on this stream, read by every lane's stream
             cache[key] = hit

@@ -159,9 +159,10 @@ _SPLIT_QUERY_CHUNK = 128
 def set_mask_head_split(on):
     """The mask head's 3 x 3 convolutions through the split-product kernels in the GPU inference path (process-wide); returns the
     previous setting."""
+    from . import fused
     global _mask_head_split
     prev, _mask_head_split = _mask_head_split, bool(on)
-    return prev
+    return fused._switched(prev, _mask_head_split)
 
 
 # DEFAULT since round 6 (TF_MASK_HEAD_FUSED_TAIL=0 / set_mask_head_fused_tail(False)): the FPN merges and the end of the mask head
@@ -170,9 +171,10 @@ _mask_head_fused_tail = os.environ.get("TF_MASK_HEAD_FUSED_TAIL", "1") != "0"
 
 
 def set_mask_head_fused_tail(on):
+    from . import fused
     global _mask_head_fused_tail
     prev, _mask_head_fused_tail = _mask_head_fused_tail, bool(on)
-    return prev
+    return fused._switched(prev, _mask_head_fused_tail)
 
 
 class MaskHeadSmallConv(nn.Module):
@@ -221,18 +223,19 @@ class MaskHeadSmallConv(nn.Module):
     @staticmethod
     def _taps(conv, cin_pad):
         """[Cout, 9 * cin_pad] tap-major weight of a 3 x 3 convolution (zero columns for the padded input channels), cached on the
-        module with the weight's version."""
+        module with the weight's fused.source_key and the parameter object itself."""
+        from . import fused
         hit = getattr(conv, "_tf_taps", None)
-        if hit is None or hit[0] != (conv.weight._version, cin_pad) or hit[1].device != conv.weight.device:
+        key = (fused.source_key(conv.weight), cin_pad)
+        if hit is None or hit[0] != key or hit[2] is not conv.weight:
             w = conv.weight.detach()
             cout, cin = w.shape[:2]
             taps = w.new_zeros(cout, 3, 3, cin_pad)
             taps[..., :cin] = w.permute(0, 2, 3, 1)
-            hit = ((conv.weight._version, cin_pad), taps.reshape(cout, 9 * cin_pad).contiguous())
+            hit = (key, taps.reshape(cout, 9 * cin_pad).contiguous(), conv.weight)
             if w.is_cuda and torch.cuda.is_current_stream_capturing():
                 return hit[1]   # built inside a graph's memory pool: part of that graph, never a cached buffer
             if w.is_cuda:
-                from . import fused
                 fused._publish_barrier(w.device)   # built on this stream, read by every sequence's stream from now on
             conv._tf_taps = hit
         return hit[1]
@@ -261,17 +264,17 @@ class MaskHeadSmallConv(nn.Module):
 
     def _taps_part(self, c0, c1):
         """[Cout, 9 * (c1 - c0)] tap-major weight of lay1 restricted to its input channels c0 .. c1 (the image part of the decomposition in
-        forward()), cached on the module with the weight's version."""
+        forward()), cached on the module like _taps."""
+        from . import fused
         conv = self.lay1
         hit = getattr(conv, "_tf_taps_part", None)
-        key = (conv.weight._version, c0, c1)
-        if hit is None or hit[0] != key or hit[1].device != conv.weight.device:
+        key = (fused.source_key(conv.weight), c0, c1)
+        if hit is None or hit[0] != key or hit[2] is not conv.weight:
             w = conv.weight.detach()[:, c0:c1]
-            hit = (key, w.permute(0, 2, 3, 1).reshape(w.shape[0], 9 * (c1 - c0)).contiguous())
+            hit = (key, w.permute(0, 2, 3, 1).reshape(w.shape[0], 9 * (c1 - c0)).contiguous(), conv.weight)
             if w.is_cuda and torch.cuda.is_current_stream_capturing():
                 return hit[1]   # built inside a graph's memory pool: part of that graph, never a cached buffer
             if w.is_cuda:
-                from . import fused
                 fused._publish_barrier(w.device)
             conv._tf_taps_part = hit
         return hit[1]

@@ -21,6 +21,59 @@ def _param_ok(t, x):
             and t.data_ptr() % 16 == 0)
 
 
+# ---------------------------------------------------------------------------------------------------------
+# COHERENCE OF THE CACHED WEIGHT IMAGES.  The inference path never reads an nn.Parameter directly: it reads an image derived from
+# it (16-bit pieces, fragment-order packings, BN-folded / tap-major convolution weights, concatenated projections), built once and
+# cached.  Every such cache keys on source_key() of each tensor it was derived from; a cache stored on a MODULE also remembers the
+# source tensor objects (same_sources): a parameter object that was replaced starts again at version 0.  What this detects by itself:
+# every write that bumps the version counter (in place under no_grad, load_state_dict, optimiser steps, writes through detach(),
+# set_) and every change of the storage or the tensor object behind a parameter (p.data = t, vector_to_parameters, module.to(),
+# load_state_dict(assign=True), a new nn.Parameter, swap_tensors, copy.deepcopy).  What it cannot: a write THROUGH `.data`
+# (p.data.mul_(), nn.init.*_(p.data)) leaves no trace on the tensor -- call weights_changed() after one.
+_weight_epoch = 0
+_route_epoch = 0              # see route_epoch() below
+
+
+def weight_epoch():
+    return _weight_epoch
+
+
+def weights_changed():
+    """Tell the library that weights were changed in a way it cannot see: a write through `.data` (`p.data.mul_(2)`,
+    `nn.init.normal_(p.data)`), which leaves the tensor's version counter, storage and identity as they were.  Bumps a process-wide
+    weight epoch that is part of every cached weight image's key: every image (split pieces, packed fragments, folded convolution
+    weights, concatenated projections, cached reference points) is rebuilt lazily at its next use, and a GraphedDetector drops its
+    captured graphs at its next call.  Everything else -- in-place writes under no_grad, load_state_dict, optimiser steps, `p.data = t`,
+    module.to(), a replaced nn.Parameter -- is detected without this call (a GraphedDetector that replays graphs notices those at
+    load_state_dict, at Tracker.reset() and at revalidate()).  Cheap to call, costly afterwards: the next forward rebuilds every
+    image.  Returns the new epoch."""
+    global _weight_epoch
+    _weight_epoch += 1
+    return _weight_epoch
+
+
+def source_key(t):
+    """The part of a cache key that stands for one source tensor (None allowed): version counter, address, device, dtype and the
+    weight epoch.  The address alone would not do (a freed parameter's address is handed to the next model's parameters by the
+    caching allocator): caches live ON the tensor object or remember it (same_sources)."""
+    if t is None:
+        return None
+    return (t._version, t.data_ptr(), t.device, t.dtype, _weight_epoch)
+
+
+def same_sources(held, srcs):
+    """The tensor OBJECTS a module-level cache was built from are the ones the module holds now."""
+    return held is not None and len(held) == len(srcs) and all(a is b for a, b in zip(held, srcs))
+
+
+def _switched(prev, new):
+    """A process-wide switch was set: what a forward enqueues changes exactly when its value does -> route_epoch()."""
+    global _route_epoch
+    if prev != new:
+        _route_epoch += 1
+    return prev
+
+
 def bias_act_(x, bias, residual=None, relu=True):
     """In place: x = act(x + bias[c] (+ residual)) for a channels_last [N,C,H,W] fp32 GPU tensor.
     Returns x, or None when the tensors do not qualify -- a residual that is x itself included -- (caller falls back to ATen ops)."""
@@ -95,7 +148,7 @@ def set_split_linear(on):
     """Switch the split-product linears on or off (process-wide); returns the previous setting."""
     global _split_linear
     prev, _split_linear = _split_linear, bool(on)
-    return prev
+    return _switched(prev, _split_linear)
 
 
 # The arithmetic of a split product (include/tf_fused.h, THE SPLIT PRODUCT; csrc/split_product.h):
@@ -142,7 +195,7 @@ def set_split_terms(n):
     global _split_terms
     n = _parse_terms(n)
     prev, _split_terms = _split_terms, n
-    return prev
+    return _switched(prev, _split_terms)
 
 
 # The same product with the weight packed once in matrix-core fragment order (tf_linear_packed_f32,
@@ -177,7 +230,7 @@ def set_packed_linear(on):
     """Switch the packed-weight kernel for the many-row linears on or off (process-wide); returns the previous setting."""
     global _packed_linear
     prev, _packed_linear = _packed_linear, bool(on)
-    return prev
+    return _switched(prev, _packed_linear)
 
 
 def _publish_barrier(device):
@@ -206,10 +259,11 @@ class one_stream:
 
 def _packed_weight(weight, rows):
     """Fragment-order image (the bf16 pieces of the current split_terms()) of `weight` (or of its row block `rows`), built by
-    tf_linear_pack_weight_f32 and cached on the tensor object with its version counter, like _split_weight below."""
+    tf_linear_pack_weight_f32 and cached on the tensor object under its source_key(), like _split_weight below."""
     cache = getattr(weight, "_tf_packed", None)
-    if cache is None or cache[0] != weight._version:
-        cache = (weight._version, {})
+    key = source_key(weight)
+    if cache is None or cache[0] != key:
+        cache = (key, {})
         weight._tf_packed = cache
     terms = _terms()
     hit = cache[1].get((rows, terms))
@@ -238,15 +292,17 @@ def _split_weight(weight):
       split_terms() 6       bf16 hi, mid, lo; scale None
       split_terms() 16      fp16 wh = f16(w t_n), wl = f16(w t_n - wh), None, and scale[n] = 16 / t_n (fp32), t_n the power of two
                             that puts the largest |w| of output channel n into [2^13, 2^14)
-    (round to nearest even at every step).  Cached ON THE TENSOR OBJECT together with its version counter
-    (weights are constants in inference; an in-place update bumps the version).  Not keyed by data_ptr: a freed
-    parameter's address is handed to the next model's parameters by the caching allocator, and a pointer-keyed cache
+    (round to nearest even at every step).  Cached ON THE TENSOR OBJECT under its source_key(): version counter (an
+    in-place update bumps it), address, device and dtype (`p.data = t`, module.to() change the storage and keep the
+    version) and the weight epoch (weights_changed(): writes through `.data`).  Not keyed by data_ptr ALONE in a table: a
+    freed parameter's address is handed to the next model's parameters by the caching allocator, and a pointer-keyed cache
     then serves another tensor's pieces (seen as a golden failure when two test models were built one after the
     other).  Callers pass persistent tensors (module parameters, _CatProjection's concatenation), and use `rows=` of
     linear() for a row block instead of a temporary slice."""
     if _terms() == 16:
         hit = getattr(weight, "_tf_split_f16", None)
-        if hit is None or hit[0] != weight._version:
+        key = source_key(weight)
+        if hit is None or hit[0] != key:
             w = weight.detach()
             amax = w.abs().amax(dim=1)
             _, e = torch.frexp(amax)                                   # amax = m 2^e with m in [0.5, 1): floor(log2 amax) = e - 1
@@ -256,7 +312,7 @@ def _split_weight(weight):
             ws = w * t[:, None]                                        # exact: powers of two
             hi = ws.to(torch.float16)
             lo = (ws - hi.float()).to(torch.float16)
-            hit = (weight._version, hi.contiguous(), lo.contiguous(), None, (16.0 / t).contiguous())
+            hit = (key, hi.contiguous(), lo.contiguous(), None, (16.0 / t).contiguous())
             if w.is_cuda and torch.cuda.is_current_stream_capturing():
                 return hit[1], hit[2], hit[3], hit[4]   # built inside a graph's memory pool: part of the graph, never a cached buffer
             if w.is_cuda:
@@ -264,13 +320,14 @@ def _split_weight(weight):
             weight._tf_split_f16 = hit
         return hit[1], hit[2], hit[3], hit[4]
     hit = getattr(weight, "_tf_split", None)
-    if hit is None or hit[0] != weight._version:
+    key = source_key(weight)
+    if hit is None or hit[0] != key:
         w = weight.detach()
         hi = w.to(torch.bfloat16)
         r = w - hi.float()                      # exact in fp32
         mid = r.to(torch.bfloat16)
         lo = (r - mid.float()).to(torch.bfloat16).contiguous()
-        hit = (weight._version, hi.contiguous(), mid.contiguous(), lo)
+        hit = (key, hi.contiguous(), mid.contiguous(), lo)
         if w.is_cuda and torch.cuda.is_current_stream_capturing():
             return hit[1], hit[2], hit[3], None   # (as above: not cached)
         if w.is_cuda:
@@ -359,7 +416,7 @@ def set_ffn_fused(on):
     """Switch the one-launch feed-forward block on or off (process-wide); returns the previous setting."""
     global _ffn_fused
     prev, _ffn_fused = _ffn_fused, bool(on)
-    return prev
+    return _switched(prev, _ffn_fused)
 
 
 def ffn(x, linear1, linear2, norm=None, residual=None):
@@ -424,7 +481,7 @@ def set_linear_ln_fused(on):
     """Switch the one-launch projection + residual + LayerNorm on or off (process-wide); returns the previous setting."""
     global _linln_fused
     prev, _linln_fused = _linln_fused, bool(on)
-    return prev
+    return _switched(prev, _linln_fused)
 
 
 def linear_residual_norm(x, linear, residual, norm):
@@ -479,7 +536,7 @@ def stem_pool_fused_enabled():
 def set_stem_pool_fused(on):
     global _stem_pool_fused
     prev, _stem_pool_fused = _stem_pool_fused, bool(on)
-    return prev
+    return _switched(prev, _stem_pool_fused)
 
 
 # DEFAULT since round 3 (TF_STEM_CONV_SPLIT=0 / set_stem_conv_split(False) switches it off): the 7 x 7 stem convolution as a split product on the matrix cores
@@ -494,14 +551,16 @@ def stem_conv_split_enabled():
 def set_stem_conv_split(on):
     global _stem_conv_split
     prev, _stem_conv_split = _stem_conv_split, bool(on)
-    return prev
+    return _switched(prev, _stem_conv_split)
 
 
 def _stem_packed(weight):
-    """Packed [64, 176] image (k = (c * 7 + ky) * 8 + kx, zero padded) of a [64, 3, 7, 7] weight, cached on the tensor."""
+    """Packed [64, 176] image (k = (c * 7 + ky) * 8 + kx, zero padded) of a [64, 3, 7, 7] weight, cached on the tensor under its
+    source_key()."""
     hit = getattr(weight, "_tf_stem_packed", None)
     terms = _terms()
-    if hit is None or hit[0] != (weight._version, terms):
+    key = (source_key(weight), terms)
+    if hit is None or hit[0] != key:
         if torch.cuda.is_current_stream_capturing():
             return None
         w = weight.detach()
@@ -513,7 +572,7 @@ def _stem_packed(weight):
             rc = _cabi.lib().tf_linear_pack_weight_f32(w2.data_ptr(), packed.data_ptr(), 176, 64, terms, _stream(w.device))
         _cabi.check(rc, "tf_linear_pack_weight_f32")
         _publish_barrier(w.device)
-        hit = ((weight._version, terms), packed)
+        hit = (key, packed)
         weight._tf_stem_packed = hit
     return hit[1]
 
@@ -573,7 +632,7 @@ def heads_split_enabled():
 def set_heads_split(on):
     global _heads_split
     prev, _heads_split = _heads_split, bool(on)
-    return prev
+    return _switched(prev, _heads_split)
 
 
 def head_linear(module, x, relu=False):
@@ -598,7 +657,7 @@ def pos_add_fused_enabled():
 def set_pos_add_fused(on):
     global _pos_add_fused
     prev, _pos_add_fused = _pos_add_fused, bool(on)
-    return prev
+    return _switched(prev, _pos_add_fused)
 
 
 def linear_add(x, x2, weight, bias=None, rows=None):
@@ -721,7 +780,7 @@ def set_conv_stream(on):
     global _conv_stream, _CONV_STREAM_ALL
     prev = "all" if (_conv_stream and _CONV_STREAM_ALL) else _conv_stream
     _conv_stream, _CONV_STREAM_ALL = bool(on), on == "all"
-    return prev
+    return _switched(prev, "all" if (_conv_stream and _CONV_STREAM_ALL) else _conv_stream)
 
 
 
@@ -736,7 +795,7 @@ def set_conv_ksplit_policy(target_blocks, leave_alone_blocks, min_slices_per_pie
     """-> the previous policy tuple."""
     global _KSPLIT_POLICY
     prev, _KSPLIT_POLICY = _KSPLIT_POLICY, (int(target_blocks), int(leave_alone_blocks), int(min_slices_per_piece), int(min_slices))
-    return prev
+    return _switched(prev, _KSPLIT_POLICY)
 
 
 def conv1x1_wants_split_k(m, cin, cout):
@@ -756,7 +815,7 @@ _CONV1X1_MIN_PIECES = 3
 def set_conv1x1_splitk(on):
     global _conv1x1_splitk
     prev, _conv1x1_splitk = _conv1x1_splitk, bool(on)
-    return prev
+    return _switched(prev, _conv1x1_splitk)
 
 
 # The halo form of the stride-1 3 x 3 convolutions (csrc/linear_stream.hip conv3x3_halo_kernel, round 6; TF_CONV_HALO=0 /
@@ -772,7 +831,7 @@ def set_conv_halo(on):
     global _conv_halo
     prev, _conv_halo = _conv_halo, bool(on)
     _cabi.lib().tf_msda_set_option(b"conv_halo", 1 if on else 0)
-    return prev
+    return _switched(prev, _conv_halo)
 
 
 def _conv_ksplit(m, k, cout, policy=None):
@@ -801,7 +860,7 @@ _input_proj_fused = os.environ.get("TF_INPUT_PROJ_FUSED", "1") != "0"
 def set_input_proj_fused(on):
     global _input_proj_fused
     prev, _input_proj_fused = _input_proj_fused, bool(on)
-    return prev
+    return _switched(prev, _input_proj_fused)
 
 
 def groupnorm_nhwc(x2, n_img, gn, relu=False):
@@ -925,13 +984,14 @@ def groupnorm_relu_conv3x3_c1(x, gn, conv):
             and not (x.data_ptr() & 15)):
         return None
     n, c, H, W = x.shape
-    hit = getattr(conv, "_tf_c1_taps", None)   # [9, C] tap-major + the bias as a Python float (one synchronising read per weight version)
-    key = (conv.weight._version, None if conv.bias is None else conv.bias._version, conv.weight.device)
-    if hit is None or hit[0] != key:
+    hit = getattr(conv, "_tf_c1_taps", None)   # [9, C] tap-major + the bias as a Python float (one synchronising read per change of the weight or the bias)
+    srcs = (conv.weight, conv.bias)
+    key = (source_key(conv.weight), source_key(conv.bias))
+    if hit is None or hit[0] != key or not same_sources(hit[3], srcs):
         if torch.cuda.is_current_stream_capturing():
             return None
         hit = conv._tf_c1_taps = (key, conv.weight.detach()[0].permute(1, 2, 0).reshape(9, c).contiguous(),
-                                  0.0 if conv.bias is None else float(conv.bias.detach()))
+                                  0.0 if conv.bias is None else float(conv.bias.detach()), srcs)
     with torch.cuda.device(x.device):
         out = torch.empty((n, 1, H, W), dtype=torch.float32, device=x.device)
         ws = torch.empty(2 * n * gn.num_groups, dtype=torch.float64, device=x.device)
@@ -954,9 +1014,10 @@ def input_proj_1x1(x, conv, gn):
             x = x.contiguous(memory_format=torch.channels_last)
         cout, cin = conv.out_channels, conv.in_channels
         hit = getattr(conv, "_tf_wtaps", None)   # persistent [Cout, 9 * Cin] tap-major image: the split pieces are cached on it
-        if hit is None or hit[0] != conv.weight._version or hit[1].device != conv.weight.device:
+        key = source_key(conv.weight)
+        if hit is None or hit[0] != key or hit[2] is not conv.weight:
             prev_img = None if hit is None else hit[1]
-            hit = (conv.weight._version, conv.weight.detach().permute(0, 2, 3, 1).reshape(cout, 9 * cin).contiguous())
+            hit = (key, conv.weight.detach().permute(0, 2, 3, 1).reshape(cout, 9 * cin).contiguous(), conv.weight)
             inherit_route(hit[1], conv.weight, prev_img)
             conv._tf_wtaps = hit
         y = conv3x3(x, hit[1], conv.bias, False, 2)
@@ -972,9 +1033,10 @@ def input_proj_1x1(x, conv, gn):
     n, cin, h, w = x.shape
     cout = conv.out_channels
     hit = getattr(conv, "_tf_w2d", None)   # persistent [Cout, Cin] view: the split pieces are cached on it
-    if hit is None or hit[0] != conv.weight._version or hit[1].device != conv.weight.device:
+    key = source_key(conv.weight)
+    if hit is None or hit[0] != key or hit[2] is not conv.weight:
         prev_img = None if hit is None else hit[1]
-        hit = (conv.weight._version, conv.weight.detach().reshape(cout, cin).contiguous())
+        hit = (key, conv.weight.detach().reshape(cout, cin).contiguous(), conv.weight)
         inherit_route(hit[1], conv.weight, prev_img)
         if hit[1].is_cuda and hit[1].data_ptr() != conv.weight.data_ptr():   # a copy made on this stream: publish for the others
             _publish_barrier(hit[1].device)
@@ -1002,7 +1064,7 @@ _box_refine_fused = os.environ.get("TF_BOX_REFINE_FUSED", "1") != "0"
 def set_box_refine_fused(on):
     global _box_refine_fused
     prev, _box_refine_fused = _box_refine_fused, bool(on)
-    return prev
+    return _switched(prev, _box_refine_fused)
 
 
 def box_refine(delta, reference_points):
@@ -1030,7 +1092,7 @@ _postprocess_fused = os.environ.get("TF_POSTPROCESS_FUSED", "1") != "0"
 def set_postprocess_fused(on):
     global _postprocess_fused
     prev, _postprocess_fused = _postprocess_fused, bool(on)
-    return prev
+    return _switched(prev, _postprocess_fused)
 
 
 def postprocess_pack(logits, boxes, img_h, img_w, clip):
@@ -1119,8 +1181,10 @@ F16_ACTIVATION_LIMIT = 65504.0 * 16.0
 _check_finite = os.environ.get("TF_SPLIT_CHECK_FINITE", "0") not in ("", "0")
 _n_six_term_routes = 0        # weights marked `_tf_six_terms` (their layers run the six-term product while the default is the fp16 one)
 _range_audit = None           # {(operation, ids of the weights): [weights, shapes, largest |activation|]} while audit_activation_range() runs
-_route_epoch = 0              # bumped whenever a route / the check / an audit changes what a forward enqueues: GraphedDetector
-                              # drops the HIP graphs it captured under another epoch (kernels are baked into a graph)
+# _route_epoch (defined at the top of the module) is bumped whenever what a forward enqueues changes: a six-term route, the finite
+# check, an audit, and every process-wide set_* switch of this module, of backbone and of detr_segmentation -- when, and only when,
+# the switch changes VALUE (_switched).  GraphedDetector drops the HIP graphs it captured under another epoch (kernels are baked into
+# a graph).  Its counterpart for the weights themselves is weight_epoch() / weights_changed().
 
 # HIP graphs (graphed.GraphedDetector, the default path of bench.py and dist_utils.track_sequences): a replay calls none of the
 # wrappers below, so (1) an audit or the finite check sees nothing inside a graph -- GraphedDetector therefore runs EAGERLY while
@@ -1139,11 +1203,9 @@ def debug_checks_active():
 
 
 def set_check_finite(on):
-    global _check_finite, _route_epoch
+    global _check_finite
     prev, _check_finite = _check_finite, bool(on)
-    if prev != _check_finite:
-        _route_epoch += 1
-    return prev
+    return _switched(prev, _check_finite)
 
 
 def _routed(weight):
@@ -1273,7 +1335,7 @@ def set_split_linear_training(flag):
     global _split_linear_train
     prev = split_linear_training_enabled()
     _split_linear_train = None if flag is None else bool(flag)
-    return prev
+    return _switched(prev, split_linear_training_enabled())
 
 
 def train_route(x):
@@ -1295,11 +1357,12 @@ class _NotApplicable(Exception):
 
 
 def _packed_weight_t(weight, terms):
-    """Fragment-order image of weight^T (the `weight` of the input gradient dx = dy . w), cached on the parameter with its version
-    counter like _packed_weight; None when it cannot be built (shape; stream capture without a cached image)."""
+    """Fragment-order image of weight^T (the `weight` of the input gradient dx = dy . w), cached on the parameter under its
+    source_key() like _packed_weight; None when it cannot be built (shape; stream capture without a cached image)."""
     cache = getattr(weight, "_tf_packed_t", None)
-    if cache is None or cache[0] != weight._version:
-        cache = (weight._version, {})
+    key = source_key(weight)
+    if cache is None or cache[0] != key:
+        cache = (key, {})
         weight._tf_packed_t = cache
     capturing = torch.cuda.is_current_stream_capturing()
     hit = cache[1].get(terms)

@@ -27,6 +27,18 @@ graph replays call none of fused's Python wrappers, so while an audit or the fin
 model EAGERLY, and graphs captured under another fused.route_epoch() are dropped (the routed kernels are baked into a graph
 at capture time: a route added later forces a new capture).
 
+Weights.  A captured graph bakes the ADDRESSES of the weight images the eager path builds from the parameters (fused.py: split
+pieces, packed fragments, folded convolution weights, ...); after a weight change the eager path builds new images and a replay
+would keep reading the old ones.  A replay does no host work on the weights, so the wrapper learns of a change at these points only:
+  * `model.load_state_dict(...)` -- the wrapper registers a post-hook on its model that bumps fused.weight_epoch();
+  * `fused.weights_changed()` -- the same epoch, bumped by hand; every call compares it (two integer compares per call);
+  * `revalidate()` -- recomputes the fingerprint of every parameter and buffer (object identity, version counter, address) and
+    drops the graphs on a difference.  It runs on the first call after construction and from `Tracker.reset()`, i.e. once per
+    sequence: an optimiser step or an in-place edit between two SEQUENCES is picked up by itself.
+A caller who edits weights by hand between two FRAMES of a sequence (in place under no_grad, `p.data = t`, a sub-module's own
+load_state_dict, an optimiser step) must call `revalidate()` -- or `fused.weights_changed()`, which a write through `.data` needs
+in any case -- before the next frame; otherwise the replays go on computing with the weights of the capture.
+
 Bucketed track-query count: in real tracking the number of track queries changes from frame to frame, and every
 count would be its own graph.  The wrapper therefore rounds the count up to a multiple of `bucket` (16) with FILLER
 track queries (zero embedding, a fixed box) that are masked out as keys of the decoder's query self-attention
@@ -58,7 +70,19 @@ import torch
 _CAPTURE_LOCK = threading.Lock()
 
 
+def _weights_loaded(module, incompatible_keys):
+    """load_state_dict post-hook of a wrapped model: every cached weight image and every captured graph is rebuilt."""
+    from . import fused
+    fused.weights_changed()
+
+
 class GraphedDetector:
+    """HIP-graph replay of `model` (module docstring).  Weights: a replay reads the weight images that existed at capture time.  The
+    wrapper drops its graphs by itself after `model.load_state_dict`, `fused.weights_changed()` and a changed `set_*` switch (at its
+    next call) and at `Tracker.reset()` / the first call (`revalidate()`: every parameter and buffer by identity, version, address).
+    A caller who edits weights BY HAND between two frames of a sequence -- an optimiser step, an in-place edit, `p.data = t`, a
+    sub-module's load_state_dict -- must call `revalidate()` (or `fused.weights_changed()`, which a write through `.data` needs
+    anyway) before the next frame: the wrapper does no host work on the weights per frame and cannot notice otherwise."""
     # `features` of a multi-frame replay are the entry's static buffers (module docstring): a caller that keeps more than
     # the latest set (Tracker with prev_frame_dist > 1) has to clone them -- Tracker.step checks this attribute
     features_alias_static_buffers = True
@@ -98,6 +122,10 @@ class GraphedDetector:
         self._side = {}           # device -> the streams prepare() runs the image-only halves on (slot i: stream i % SIDE_STREAMS)
         self._generation = 0      # prepare() calls so far: a static image is only "prepared" for the call that follows ITS prepare()
         self._epoch = None        # fused.route_epoch() the graphs were captured under
+        self._wepoch = None       # fused.weight_epoch() the graphs were captured under
+        self._fingerprint = None  # (tensors, [(version, address)]) of the model's parameters and buffers at the last revalidate()
+        if isinstance(model, torch.nn.Module) and "_tf_weights_hook" not in model.__dict__:   # (one hook per model, not per wrapper / lane)
+            model.__dict__["_tf_weights_hook"] = model.register_load_state_dict_post_hook(_weights_loaded)
 
     def _configure(self, lanes, lane=0):
         import os
@@ -136,15 +164,41 @@ class GraphedDetector:
     def _sync_epoch(self):
         """Graphs bake the kernels of the fused routes they were captured under: drop them when the routes changed."""
         from . import fused
-        epoch = fused.route_epoch()
-        if epoch != self._epoch:
-            if self._graphs or self._enc:
-                torch.cuda.synchronize()
-                self._graphs.clear()
-                self._enc.clear()
-                self._seen.clear()
-                self._fifo = []
-            self._epoch = epoch
+        if fused._route_epoch != self._epoch or fused._weight_epoch != self._wepoch:
+            self._drop_graphs()
+            self._epoch, self._wepoch = fused._route_epoch, fused._weight_epoch
+            self._fingerprint = self._fingerprint_now()
+        elif self._fingerprint is None:   # the first call after construction
+            self.revalidate()
+
+    def _drop_graphs(self):
+        if self._graphs or self._enc:
+            torch.cuda.synchronize()
+            self._graphs.clear()
+            self._enc.clear()
+            self._seen.clear()
+            self._fifo = []
+
+    def _fingerprint_now(self):
+        m = self.model
+        if not isinstance(m, torch.nn.Module):
+            return ([], [])
+        ts = list(m.parameters()) + list(m.buffers())
+        return (ts, [(t._version, t.data_ptr()) for t in ts])   # (the tensor objects are held: compared with `is`)
+
+    def revalidate(self):
+        """Compare every parameter and buffer of the model (object identity, version counter, address) with what they were at the
+        last check and drop the captured graphs if any differs; True when nothing changed.  Called by the first call after
+        construction and by Tracker.reset() (once per sequence); call it yourself after changing weights between two frames (see the
+        module docstring, Weights).  A walk over the model: hundreds of microseconds, which is why a replay does not do it."""
+        now = self._fingerprint_now()
+        old = self._fingerprint
+        same = (old is not None and len(old[0]) == len(now[0]) and all(a is b for a, b in zip(old[0], now[0])) and old[1] == now[1])
+        if not same:
+            if old is not None:
+                self._drop_graphs()
+            self._fingerprint = now
+        return same
 
     def _capturable(self, img, target, prev_features):
         from . import fused

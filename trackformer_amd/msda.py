@@ -284,18 +284,19 @@ class _CatProjection:
 
     def __init__(self):
         self.key = None
+        self.srcs = None
         self.weight = None
         self.bias = None
 
     def get(self, mod):
         srcs = (mod.sampling_offsets.weight, mod.sampling_offsets.bias,
                 mod.attention_weights.weight, mod.attention_weights.bias)
-        key = tuple((t.data_ptr(), t._version, t.device, t.dtype) for t in srcs)
-        if key != self.key:
+        key = tuple(fused.source_key(t) for t in srcs)
+        if key != self.key or not fused.same_sources(self.srcs, srcs):
             with torch.no_grad():
                 self.weight = torch.cat([srcs[0], srcs[2]], 0).contiguous()
                 self.bias = torch.cat([srcs[1], srcs[3]], 0).contiguous()
-            self.key = key
+            self.key, self.srcs = key, srcs
         return self.weight, self.bias
 
 
@@ -358,7 +359,10 @@ class MSDeformAttn(nn.Module):
         # modules/ms_deform_attn.py:34-47.  The 8-direction table of the reference is the set of
         # unit steps ordered (-1,-1),(-1,0),(-1,1),(0,-1),(0,1),(1,-1),(1,0),(1,1); like the
         # reference it only fits n_heads == 8.
-        constant_(self.sampling_offsets.weight.data, 0.)
+        # (in place on the parameters under no_grad, never through `.data`: a write through `.data` leaves no trace for the caches of
+        # the weight images, and _reset_parameters() of a module that has already run would go unnoticed)
+        with torch.no_grad():
+            constant_(self.sampling_offsets.weight, 0.)
         dirs = [(a, b) for a in (-1, 0, 1) for b in (-1, 0, 1) if (a, b) != (0, 0)]
         if self.n_heads != len(dirs):
             raise ValueError("MSDeformAttn bias initialisation requires n_heads == 8")
@@ -367,12 +371,12 @@ class MSDeformAttn(nn.Module):
         scale = torch.arange(1, self.n_points + 1, dtype=torch.float32).view(1, 1, -1, 1)
         with torch.no_grad():
             self.sampling_offsets.bias = nn.Parameter((grid * scale).reshape(-1))
-        constant_(self.attention_weights.weight.data, 0.)
-        constant_(self.attention_weights.bias.data, 0.)
-        xavier_uniform_(self.value_proj.weight.data)
-        constant_(self.value_proj.bias.data, 0.)
-        xavier_uniform_(self.output_proj.weight.data)
-        constant_(self.output_proj.bias.data, 0.)
+            constant_(self.attention_weights.weight, 0.)
+            constant_(self.attention_weights.bias, 0.)
+            xavier_uniform_(self.value_proj.weight)
+            constant_(self.value_proj.bias, 0.)
+            xavier_uniform_(self.output_proj.weight)
+            constant_(self.output_proj.bias, 0.)
 
     def forward(self, query, reference_points, input_flatten, input_spatial_shapes,
                 input_padding_mask=None, query_attn_mask=None, residual_norm=None, query_pos=None):

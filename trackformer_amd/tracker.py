@@ -115,6 +115,9 @@ class Tracker:
         self._prev_features = deque([None], maxlen=self.prev_frame_dist)
         self._inflight_features = None
         self._prepared = None
+        revalidate = getattr(self.obj_detector, "revalidate", None)
+        if revalidate is not None:   # GraphedDetector: once per sequence, notice weights changed since its graphs were captured
+            revalidate()
         if hard:
             self.track_num = 0
             self._results = {}
