@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define TF_MSDA_ABI_VERSION 5
+#define TF_MSDA_ABI_VERSION 6
 #define TF_MSDA_MAX_LEVELS 16
 
 typedef enum tf_msda_status {
@@ -231,6 +231,49 @@ int tf_msda_backward_det_f64_dshapes(const double *value, const int64_t *shapes_
                                      const double *grad_out, double *grad_value, double *grad_loc, double *grad_attn,
                                      void *workspace, int64_t workspace_bytes, int N, int S, int M, int D, int L, int Lq, int P,
                                      void *stream);
+
+/*
+ * Training through the fused entry (fp32).  tf_msda_forward_fused_f32 keeps neither loc nor attn; these two entries let a
+ * backward recompute them and carry the gradients of the operator's backward back to the RAW projection, so that a caller
+ * (trackformer_amd.msda.ms_deform_attn_fused) saves only value, ref_points and qproj:
+ *     tf_msda_fused_prologue_f32 -> tf_msda_backward_f32 or tf_msda_backward_det_f32 on (loc, attn) -> tf_msda_fused_backward_epilogue_f32
+ * Arguments as tf_msda_forward_fused_f32 (ref_points, ref_dim, qproj, ld, off_col, logit_col, shapes_hw_host); there is no
+ * value and no S: the level shapes only supply the divisors of the 2-d formula, so TF_MSDA_ERR_SHAPE_SUM cannot occur here.
+ *
+ * tf_msda_fused_prologue_f32 writes the fused entry's own prologue (csrc/msda_fused_bwd.h):
+ *   loc  [N, Lq, M, L, P, 2]   ref_dim 2: ref + off / (H_l, W_l)   (x over H_l, as above);  ref_dim 4: ref[:2] + off / P * ref[2:] * 0.5
+ *   attn [N, Lq, M, L, P]      softmax over the head's L*P logits (max-subtracted exponential)
+ *   in plain fp32 (IEEE division and add, __expf): within 2^-22 |off term| + 2^-23 |loc| and within the softmax bound of
+ *   tests/util_msda_numerics.py (fused_locations) of the float64 result.  The forward kernels round the same formulas in their
+ *   own way (v_rcp_f32 in the LDS-window kernels), so loc / attn agree with what the forward sampled to those bounds, not bit for bit.
+ *
+ * tf_msda_fused_backward_epilogue_f32: with a = attn, ga = grad_attn, gl = grad_loc (both as tf_msda_backward_* writes them)
+ *   grad_logit_i        = a_i (ga_i - sum_j a_j ga_j)                      j over the head's L*P, in index order
+ *   grad_off            = gl / (H_l, W_l)        (ref_dim 2)      gl * ref[2:] * 0.5 / P   (ref_dim 4)
+ *   grad_ref[n,q,l,:2]  = sum_{m,p} gl                                     (m, p) in index order
+ *   grad_ref[n,q,l,2:]  = sum_{m,p} gl * off * 0.5 / P                     (ref_dim 4)
+ *   A sample out of range (the operator kernels' test, -1 < fma(loc, size, -0.5) < size per coordinate, on the location the prologue
+ *   writes) takes no part in the forward: its ga / gl are read as 0 whatever the buffers hold.  tf_msda_backward_* leaves 0 there for
+ *   finite inputs (nothing changes) but NaN * 0 = NaN under a NaN in grad_out, where the gradient is 0.
+ *   grad_qproj [N*Lq, ld_g]: row r receives grad_off in columns [goff_col, goff_col + 2*M*L*P) and grad_logit in
+ *   [glogit_col, glogit_col + M*L*P) (the layout of qproj, with its own ld_g / columns; the two ranges must not overlap);
+ *   every other element of the buffer is left alone.  grad_ref [N, Lq, L, ref_dim] may be NULL: it is then not computed.
+ *
+ * Both: no atomic of any kind, every output element is written once by a plain store, every sum runs in an order the
+ * dimensions fix: the results are bit-identical across calls, streams and HIP-graph replay.  Only kernels are enqueued on
+ * `stream` (no memset, no workspace): HIP-graph capturable.
+ * Requires L <= TF_MSDA_MAX_LEVELS, P in {1,2,4,8}, ref_dim in {2,4}, M*L*P <= 2048 (a workgroup stages whole rows in LDS),
+ * even ld / off_col / ld_g / goff_col, columns inside ld / ld_g, 8-byte aligned qproj / loc / grad_loc / grad_qproj, tensors < 4 GiB.
+ * Status: NULL pointer (grad_ref excepted) -> TF_MSDA_ERR_NULL_POINTER, then everything else -> TF_MSDA_ERR_BAD_DIMS, before any GPU work.
+ * tf_msda_last_kernel() reports "msda_fused_prologue<f32>" / "msda_fused_bwd_epilogue<f32>".
+ */
+int tf_msda_fused_prologue_f32(const float *ref_points, int ref_dim, const float *qproj, int ld, int off_col, int logit_col,
+                               const int64_t *shapes_hw_host, float *loc, float *attn, int N, int M, int L, int Lq, int P,
+                               void *stream);
+int tf_msda_fused_backward_epilogue_f32(const float *ref_points, int ref_dim, const float *qproj, int ld, int off_col,
+                                        int logit_col, const int64_t *shapes_hw_host, const float *attn, const float *grad_loc,
+                                        const float *grad_attn, float *grad_qproj, int ld_g, int goff_col, int glogit_col,
+                                        float *grad_ref, int N, int M, int L, int Lq, int P, void *stream);
 
 /*
  * The operator for HOST tensors: every pointer is a host pointer, the call computes synchronously on the calling thread

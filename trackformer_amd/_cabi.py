@@ -32,6 +32,8 @@ EXPORTED_SYMBOLS = (
     "tf_msda_backward_det_f64",
     "tf_msda_backward_det_f32_dshapes",
     "tf_msda_backward_det_f64_dshapes",
+    "tf_msda_fused_prologue_f32",
+    "tf_msda_fused_backward_epilogue_f32",
     "tf_msda_forward_host_f32",
     "tf_msda_forward_host_f64",
     "tf_msda_backward_host_f32",
@@ -72,7 +74,7 @@ EXPORTED_SYMBOLS = (
     "tf_nms_host_f32",
 )
 
-ABI_VERSION = 5   # 5: tf_linear_grad_stats / wgrad / dgrad (4: tf_msda_backward_det_* and TF_MSDA_ERR_WORKSPACE; 3: the split-product entry points take w_lo / w_scale / terms)
+ABI_VERSION = 6   # 6: tf_msda_fused_prologue / _backward_epilogue (5: tf_linear_grad_stats / wgrad / dgrad; 4: tf_msda_backward_det_* and TF_MSDA_ERR_WORKSPACE; 3: the split-product entry points take w_lo / w_scale / terms)
 
 _lib = None
 
@@ -133,6 +135,10 @@ def lib():
     L.tf_nms_host_f32.argtypes = [vp, vp, ci, ctypes.c_float, vp, vp]
     L.tf_msda_forward_fused_f32.restype = ci
     L.tf_msda_forward_fused_f32.argtypes = [vp, vp, vp, ci, vp, ci, ci, ci, vp] + [ci] * 7 + [vp]
+    L.tf_msda_fused_prologue_f32.restype = ci
+    L.tf_msda_fused_prologue_f32.argtypes = [vp, ci, vp, ci, ci, ci, vp, vp, vp] + [ci] * 5 + [vp]
+    L.tf_msda_fused_backward_epilogue_f32.restype = ci
+    L.tf_msda_fused_backward_epilogue_f32.argtypes = [vp, ci, vp, ci, ci, ci, vp, vp, vp, vp, vp, ci, ci, ci, vp] + [ci] * 5 + [vp]
     L.tf_bias_act_f32.restype = ci
     L.tf_bias_act_f32.argtypes = [vp, vp, vp, ctypes.c_int64, ci, ci, vp]
     L.tf_add_layernorm_f32.restype = ci

@@ -2229,6 +2229,7 @@ int backward_impl(const T *value, const int64_t *shapes_host, const int64_t *sha
 }
 
 #include "msda_bwd_det.h"
+#include "msda_fused_bwd.h"
 
 }  // namespace
 
@@ -2417,6 +2418,22 @@ int tf_msda_backward_det_f64_dshapes(const double *value, const int64_t *shapes_
     if (!shapes_hw_dev) return TF_MSDA_ERR_NULL_POINTER;
     return backward_det_impl<double>(value, nullptr, shapes_hw_dev, loc, attn, grad_out, grad_value, grad_loc, grad_attn,
                                      workspace, workspace_bytes, N, S, M, D, L, Lq, P, stream);
+}
+
+int tf_msda_fused_prologue_f32(const float *ref_points, int ref_dim, const float *qproj, int ld, int off_col, int logit_col,
+                               const int64_t *shapes_hw_host, float *loc, float *attn, int N, int M, int L, int Lq, int P,
+                               void *stream)
+{
+    return fused_prologue_impl(ref_points, ref_dim, qproj, ld, off_col, logit_col, shapes_hw_host, loc, attn, N, M, L, Lq, P,
+                               stream);
+}
+int tf_msda_fused_backward_epilogue_f32(const float *ref_points, int ref_dim, const float *qproj, int ld, int off_col,
+                                        int logit_col, const int64_t *shapes_hw_host, const float *attn, const float *grad_loc,
+                                        const float *grad_attn, float *grad_qproj, int ld_g, int goff_col, int glogit_col,
+                                        float *grad_ref, int N, int M, int L, int Lq, int P, void *stream)
+{
+    return fused_bwd_epilogue_impl(ref_points, ref_dim, qproj, ld, off_col, logit_col, shapes_hw_host, attn, grad_loc, grad_attn,
+                                   grad_qproj, ld_g, goff_col, glogit_col, grad_ref, N, M, L, Lq, P, stream);
 }
 
 }  // extern "C"

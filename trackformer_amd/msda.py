@@ -231,6 +231,19 @@ def ms_deform_attn_backward(value, spatial_shapes, sampling_loc, attn_weight, gr
     return [grad_value, grad_loc, grad_attn]
 
 
+def _qproj_rows(qproj):
+    """(qproj, ld) as the fused entries read it: row (b, q) of qproj at (b * Lq + q) * ld.  A view whose columns are adjacent and
+    whose batches are Lq rows apart (a column slice of a wider projection) is passed with its row stride, anything else as a
+    contiguous copy."""
+    N, Lq = qproj.shape[:2]
+    ld = qproj.stride(1)
+    if not (Lq > 1 and qproj.stride(2) == 1 and (N == 1 or qproj.stride(0) == Lq * ld) and ld >= qproj.shape[-1]
+            and ld % 2 == 0 and qproj.data_ptr() % 8 == 0):
+        qproj = qproj.contiguous()
+        ld = qproj.shape[-1]
+    return qproj, ld
+
+
 def ms_deform_attn_forward_fused(value, spatial_shapes, reference_points, qproj, n_heads, n_levels,
                                  n_points):
     """Inference-only fused operator: softmax + sampling-location arithmetic + sampling in one launch.
@@ -259,13 +272,7 @@ def ms_deform_attn_forward_fused(value, spatial_shapes, reference_points, qproj,
             or tuple(reference_points.shape[:3]) != (N, Lq, L):
         raise RuntimeError("ms_deform_attn_forward_fused: inconsistent tensor shapes")
     reference_points = reference_points.contiguous()
-    # the kernels read row (b, q) of qproj at (b * Lq + q) * ld: a view whose columns are adjacent and whose batches are Lq rows
-    # apart (a column slice of a wider projection) is passed with its row stride, anything else as a contiguous copy
-    ld = qproj.stride(1)
-    if not (Lq > 1 and qproj.stride(2) == 1 and (N == 1 or qproj.stride(0) == Lq * ld) and ld >= qproj.shape[-1]
-            and ld % 2 == 0 and qproj.data_ptr() % 8 == 0):
-        qproj = qproj.contiguous()
-        ld = qproj.shape[-1]
+    qproj, ld = _qproj_rows(qproj)
     lib = _cabi.lib()
     with torch.cuda.device(value.device):
         out = torch.empty((N, Lq, M * D), dtype=value.dtype, device=value.device)
@@ -298,6 +305,101 @@ class _CatProjection:
                 self.bias = torch.cat([srcs[1], srcs[3]], 0).contiguous()
             self.key, self.srcs = key, srcs
         return self.weight, self.bias
+
+
+# TRAINING THROUGH THE FUSED ENTRY (opt-in).  With gradients enabled MSDeformAttn runs the reference's module graph: two linears,
+# view / softmax / division / add over [N, Lq, M, L, P, 2] and MSDeformAttnFunction, and its backward walks the same ATen chain in
+# reverse.  set_fused_training(True) / TF_MSDA_FUSED_TRAIN=1 trains through the operator that is deployed instead: ONE linear over
+# the concatenated (sampling_offsets | attention_weights) parameters and ms_deform_attn_fused, whose backward recomputes loc / attn
+# (tf_msda_fused_prologue_f32), runs the operator's own backward and carries its gradients back to the raw projection
+# (tf_msda_fused_backward_epilogue_f32).  OFF by default: whether a training step is faster with it is a measurement
+# (tools/bench_msda_fused_train.py, profiles/msda_fused_train_bench.json), not a promise.
+_fused_training = None   # None: follow TF_MSDA_FUSED_TRAIN (unset: off)
+_FUSED_TRAIN_MAX_ROW_SAMPLES = 2048   # M*L*P the prologue / epilogue entries take (include/tf_msda.h); beyond it: today's graph
+_fused_train_counts = {"fused": 0, "reference": 0}
+
+
+def fused_training_enabled():
+    if _fused_training is not None:
+        return _fused_training
+    return _os.environ.get("TF_MSDA_FUSED_TRAIN", "0") not in ("", "0")
+
+
+def set_fused_training(flag):
+    """Switch training through the fused entry on or off (process-wide; None: follow TF_MSDA_FUSED_TRAIN again); returns the
+    previous setting."""
+    global _fused_training
+    prev = fused_training_enabled()
+    _fused_training = None if flag is None else bool(flag)
+    return prev
+
+
+def fused_train_counts(reset=False):
+    """With the switch on: how many MSDeformAttn forwards with gradients enabled took the fused path and how many the reference's
+    module graph (a query_attn_mask, host tensors, no host shapes, another dtype or shape)."""
+    out = dict(_fused_train_counts)
+    if reset:
+        for k in _fused_train_counts:
+            _fused_train_counts[k] = 0
+    return out
+
+
+class MSDeformAttnFusedFunction(Function):
+    """ms_deform_attn_fused: the fused entry with a backward.  Saves value, the reference points and qproj only."""
+
+    @staticmethod
+    def forward(ctx, value, spatial_shapes, reference_points, qproj, n_heads, n_levels, n_points, deterministic):
+        ctx.host_shapes = _host_shapes_of(spatial_shapes)
+        ctx.dims = (n_heads, n_levels, n_points)
+        ctx.deterministic = deterministic
+        output = ms_deform_attn_forward_fused(value, spatial_shapes, reference_points, qproj, n_heads, n_levels, n_points)
+        ctx.save_for_backward(value, spatial_shapes, reference_points, qproj)
+        return output
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_output):
+        value, spatial_shapes, reference_points, qproj = ctx.saved_tensors
+        attach_host_shapes(spatial_shapes, ctx.host_shapes)
+        M, L, P = ctx.dims
+        N, Lq = qproj.shape[:2]
+        mlp = M * L * P
+        ref_dim = reference_points.shape[-1]
+        need_value, _, need_ref, need_q = ctx.needs_input_grad[:4]
+        reference_points = reference_points.contiguous()
+        qproj, ld = _qproj_rows(qproj)
+        lib = _cabi.lib()
+        shp = ctypes.cast(_shape_array(ctx.host_shapes), ctypes.c_void_p)
+        with torch.cuda.device(value.device):
+            stream = torch.cuda.current_stream().cuda_stream
+            loc = torch.empty((N, Lq, M, L, P, 2), dtype=torch.float32, device=value.device)
+            attn = torch.empty((N, Lq, M, L, P), dtype=torch.float32, device=value.device)
+            rc = lib.tf_msda_fused_prologue_f32(reference_points.data_ptr(), ref_dim, qproj.data_ptr(), ld, 0, 2 * mlp, shp,
+                                                loc.data_ptr(), attn.data_ptr(), N, M, L, Lq, P, stream)
+            _cabi.check(rc, "ms_deform_attn_fused (prologue)")
+            grad_value, grad_loc, grad_attn = ms_deform_attn_backward(value, spatial_shapes, loc, attn, grad_output,
+                                                                      deterministic=ctx.deterministic)
+            grad_q = grad_ref = None
+            if need_q or need_ref:
+                grad_q = torch.empty((N, Lq, 3 * mlp), dtype=torch.float32, device=value.device)
+                grad_ref = torch.empty_like(reference_points) if need_ref else None
+                rc = lib.tf_msda_fused_backward_epilogue_f32(
+                    reference_points.data_ptr(), ref_dim, qproj.data_ptr(), ld, 0, 2 * mlp, shp, attn.data_ptr(),
+                    grad_loc.data_ptr(), grad_attn.data_ptr(), grad_q.data_ptr(), 3 * mlp, 0, 2 * mlp,
+                    0 if grad_ref is None else grad_ref.data_ptr(), N, M, L, Lq, P, stream)
+                _cabi.check(rc, "ms_deform_attn_fused (epilogue)")
+        return (grad_value if need_value else None, None, grad_ref, grad_q if need_q else None, None, None, None, None)
+
+
+def ms_deform_attn_fused(value, spatial_shapes, reference_points, qproj, n_heads, n_levels, n_points, deterministic=None):
+    """ms_deform_attn_forward_fused with gradients (fp32 device tensors, host shapes attached): the output is that entry's, bit for
+    bit; the backward returns the gradients with respect to value, reference_points and the RAW projection qproj
+    [N, Lq, 3*M*L*P] -- tf_msda_fused_prologue_f32 (loc / attn again, nothing but the three inputs is saved), then
+    ms_deform_attn_backward(..., deterministic=deterministic) (None: see deterministic_backward_enabled, resolved at backward
+    time), then tf_msda_fused_backward_epilogue_f32.  Apart from the operator's backward no float atomic is involved: with
+    deterministic=True all three gradients are bit-identical from call to call.  Not differentiable twice."""
+    return MSDeformAttnFusedFunction.apply(value, spatial_shapes, reference_points, qproj, n_heads, n_levels, n_points,
+                                           deterministic)
 
 
 class MSDeformAttnFunction(Function):
@@ -438,6 +540,22 @@ class MSDeformAttn(nn.Module):
 
         if query_pos is not None:
             query = query + query_pos
+        if torch.is_grad_enabled() and fused_training_enabled():
+            if (hs is not None and query_attn_mask is None and value.is_cuda and value.dtype == torch.float32
+                    and query.is_cuda and query.dtype == torch.float32 and reference_points.is_cuda
+                    and reference_points.dtype == torch.float32 and reference_points.shape[-1] in (2, 4)
+                    and (self.d_model // M) % 4 == 0 and P in (1, 2, 4, 8) and M * L * P <= _FUSED_TRAIN_MAX_ROW_SAMPLES):
+                # training through the deployed operator: ONE linear over a differentiable concatenation (autograd splits dW / db
+                # back to the two modules; the weight images fused caches on the temporary die with it), then the fused entry
+                _fused_train_counts["fused"] += 1
+                w = torch.cat([self.sampling_offsets.weight, self.attention_weights.weight], 0)
+                b = torch.cat([self.sampling_offsets.bias, self.attention_weights.bias], 0)
+                qproj = fused.linear_train(query, w, b) if fused.train_route(query) else None
+                if qproj is None:
+                    qproj = F.linear(query, w, b)
+                output = ms_deform_attn_fused(value, input_spatial_shapes, reference_points, qproj, M, L, P)
+                return fused.module_linear(self.output_proj, output, False)
+            _fused_train_counts["reference"] += 1
         sampling_offsets = fused.module_linear(self.sampling_offsets, query, False).view(N, Len_q, M, L, P, 2)
         attention_weights = fused.module_linear(self.attention_weights, query, False).view(N, Len_q, M, L * P)
         attention_weights = F.softmax(attention_weights, -1).view(N, Len_q, M, L, P)
