@@ -368,6 +368,33 @@ int tf_ffn_fused_f32(const float *x, const void *w1_packed, const float *b1, con
                      int d_model, int d_ffn, int terms, void *stream);
 
 /*
+ * Several projections of the same rows in one launch (trackformer_amd/csrc/ffn_fused.hip): for each of `ngroups` (1..8) groups
+ *
+ *     y_g[M, N_g] = (add_x2 ? x + x2 : x)[M, K] . w_g^T + bias_g
+ *
+ * -- the value projection and the query projection of `with_pos_embed(src, pos)` of an encoder layer (reference:
+ * models/ops/modules/ms_deform_attn.py:64-72 under models/deformable_transformer.py:279-283), or the value projections of all
+ * decoder layers' cross-attention over the one encoder memory.  A workgroup stages its rows of x once (and once more as x + x2, the
+ * fp32 sum rounded before it is split) and walks every group's weight; the groups without add_x2 run first.  Same split product
+ * as tf_linear_split_f32 / tf_linear_split_add_f32 with the same `terms`: every y_g is bit-identical to theirs.
+ *   w_packed   tf_linear_pack_weight_f32(K, N_g, terms) of that group's weight alone (with its own channel scales)
+ *   bias       [N_g] or NULL;  y: its own contiguous [M, N_g] buffer, distinct from x, x2 and every other y
+ *   x2         [M, K], required if any group has add_x2
+ * K == 256 (else TF_MSDA_ERR_BAD_DIMS: the caller keeps the separate launches), N_g % 32 == 0, (M + 128) N_g 4 < 2^32, every pointer
+ * 16-byte aligned.  The descriptors are read during the call (they travel in the kernel's arguments): `groups` may be a temporary.
+ * NULL pointer -> TF_MSDA_ERR_NULL_POINTER, then dimensions / alignment -> TF_MSDA_ERR_BAD_DIMS, before any GPU work.
+ */
+typedef struct tf_proj_group {
+    const void *w_packed;
+    const float *bias;
+    float *y;
+    int N;
+    int add_x2;
+} tf_proj_group;
+int tf_linear_groups_f32(const float *x, const float *x2, const tf_proj_group *groups, int ngroups, int64_t M, int K, int terms,
+                         void *stream);
+
+/*
  * out[n, l, h, :] = sum_j softmax_j(scale * q[n, l, h, :] . k[n, j, h, :]) v[n, j, h, :]      (fp32)
  * Element (n, l, h, c) of q / k / v / out lives at base + (n * L + l) * ld + h * D + c with ld in floats (so q and
  * k may be the two halves of one projection output).  key_mask: [N, Lk] bytes, non-zero = the key is ignored

@@ -98,6 +98,7 @@ int tf_msda_set_tiled(int mode);
  *   "direct9"       1 / 0: msda_fwd_f32_direct9 for D == 36 decoder calls (off: msda_fwd_f32_buf)
  *   "ffn_ti" "linln_ti" "linear_stream_ti"   row tiles per block of tf_ffn_fused_f32 / tf_linear_res_ln_f32 /
  *                   tf_linear_packed_f32 (include/tf_fused.h; 0 = per shape)
+ *   "groups_ti"     row tiles per block of tf_linear_groups_f32 with fp16 pieces (1..3; 0 = by row count, the default)
  *   "wgrad_msplit"  chunks the row loop of tf_linear_wgrad_split_f32 is cut into (1..64; 0 = per shape, the default).  Unlike the
  *                   other knobs it changes the summation order of dw -- and the workspace tf_linear_wgrad_workspace_bytes asks for
  * Knobs of experiments that were measured and removed (linear_variant, linear_bufstore, linear_deep, linear_astat,

@@ -69,6 +69,7 @@ EXPORTED_SYMBOLS = (
     "tf_linear_split_add_f32",
     "tf_ffn_fused_f32",
     "tf_linear_res_ln_f32",
+    "tf_linear_groups_f32",
     "tf_conv_packed_f32",
     "tf_mha_core_f32",
     "tf_nms_host_f32",
@@ -77,6 +78,12 @@ EXPORTED_SYMBOLS = (
 ABI_VERSION = 6   # 6: tf_msda_fused_prologue / _backward_epilogue (5: tf_linear_grad_stats / wgrad / dgrad; 4: tf_msda_backward_det_* and TF_MSDA_ERR_WORKSPACE; 3: the split-product entry points take w_lo / w_scale / terms)
 
 _lib = None
+
+
+class ProjGroup(ctypes.Structure):
+    """tf_proj_group of include/tf_fused.h (tf_linear_groups_f32)."""
+    _fields_ = [("w_packed", ctypes.c_void_p), ("bias", ctypes.c_void_p), ("y", ctypes.c_void_p), ("N", ctypes.c_int),
+                ("add_x2", ctypes.c_int)]
 
 
 class MSDAError(RuntimeError):
@@ -184,6 +191,8 @@ def lib():
     L.tf_linear_res_ln_f32.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_float, vp, ctypes.c_int64, ci, ci, ci, vp]
     L.tf_ffn_fused_f32.restype = ci
     L.tf_ffn_fused_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_float, vp, ctypes.c_int64, ci, ci, ci, vp]
+    L.tf_linear_groups_f32.restype = ci
+    L.tf_linear_groups_f32.argtypes = [vp, vp, ctypes.POINTER(ProjGroup), ci, ctypes.c_int64, ci, ci, vp]
     L.tf_linear_split_add_f32.restype = ci
     L.tf_linear_split_add_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_int64, ci, ci, vp]
     L.tf_linear_packed_f32.restype = ci

@@ -533,6 +533,7 @@ int linln_ti()
     return v;
 }
 
+std::atomic<int> g_groups_ti{0};   // tf_linear_groups_f32, fp16 pieces: row tiles per block (1..3); 0: by row count
 std::atomic<int> g_ffn_tail{-1};   // -1: TF_FFN_TAIL_SPLIT or the default (1): the rows behind the full rounds as 32-row blocks
 std::atomic<int> g_ffn_ti{-1};   // -1: TF_FFN_TI or the default (3)
 int ffn_ti()
@@ -572,6 +573,7 @@ int ffn_set_ti(int v)
     g_ffn_ti.store(v >= 1 && v <= 3 ? v : 3);
     return prev;
 }
+int groups_set_ti(int v) { return g_groups_ti.exchange(v >= 1 && v <= 3 ? v : 0); }
 int linln_set_ti(int v)
 {
     const int prev = linln_ti();
@@ -672,7 +674,310 @@ int dispatch_ffn_scheme(int sp, const float *x, const u32x4 *w1, const float *b1
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// tf_linear_groups_f32: several projections of ONE token tile in one launch,  y_g = (add_x2 ? x + x2 : x) . W_g^T + bias_g  for up
+// to 8 weights (include/tf_fused.h) -- linear_res_ln_kernel without residual / LayerNorm and with an outer loop over the weights.
+// Why: the encoder's value projection (x) and query projection (x + pos), and the six decoder layers' value projections of the
+// same memory, each re-fetched and re-split the same 22 223 x 256 rows per launch and per 128-wide column block of a launch.
+//   * A block owns 32 TI rows (TI = 3 at many rows, fp16 pieces: 232 blocks for 22 223 rows, one round; else 32-row blocks).  The x
+//     tile is staged ONCE as its 16-bit pieces; the groups without add_x2 run first (in the caller's order), then the tile is
+//     staged again as split(fl32(x + x2)) -- the fp32 add first, then the split, as split_gemm_body's XADD -- for the others.
+//     x is re-read (from L2: the block read it a few microseconds ago) for the second staging: holding it would cost 96 VGPRs
+//     through the first phase (of 400 in use at 96 rows).  NOT MEASURED: neither holding x, nor issuing the second staging's
+//     loads under the previous group's MFMAs -- the restage is barrier, load, split, barrier, with only the ring's weight
+//     prefetches of the next group in flight across it.  The estimate of 35 us for the encoder pair was missed (53 us); these two
+//     are untried, and the three block sizes measuring alike suggests the staging sequence is not what bounds the launch.
+//   * A group is walked in CHUNKS: 256 columns (each wave two 32-wide tiles, a weight unit = one k-step of both), then, for what
+//     is left (N = 384 -> 128 columns; the packed image pads to 512), 128 columns with ONE tile per wave (a unit = two k-steps of
+//     that tile: the same 2 NB fragments per lane, so the ring keeps its shape) -- all four waves busy, nobody multiplies padding.
+//     Tiles at or beyond N (N % 128 != 0) are computed on the image's zero padding and not stored.
+//   * The weight ring carries on across chunk, group and staging boundaries (the next chunk's first units are requested during the
+//     last k-steps of this one); biases and channel scales of ALL groups are put into LDS while the first tile is staged, so a
+//     chunk's epilogue waits for nothing that was issued after the ring's prefetches (vmcnt counts in order) and holds them in
+//     registers only while it runs; the buffer stores of a chunk are not waited for: they drain under the next
+//     chunk's MFMAs (the first wait behind them is for a weight unit issued six k-steps earlier).
+//   * Same arithmetic as every dense kernel here (per k-step the terms smallest first, k ascending; epilogue fma(acc, r_n, bias) /
+//     acc + bias): bit-identical to tf_linear_split_f32 / tf_linear_split_add_f32 / tf_linear_packed_f32.
+// Hidden 288 is not built (three waves of three tiles: another chunk geometry); the entry refuses K != 256 and the callers keep the
+// separate launches.  Rows per block (fp16 pieces): 96 from 4096 rows on, 32 below; tf_msda_set_option("groups_ti", 1 | 2 | 3) forces
+// 32 / 64 / 96 (0: by row count); six terms always run 32-row blocks.
+// Measured (MI355X, 22 223 rows, cold caches, profiles/proj_groups_bench.json): the encoder pair 53.3 us against 61.2 for the two
+// launches it replaces, six 256-wide weights 77.9 against 124.2; 32- and 64-row blocks: 51.8 / 56.7 and 86.5 / 88.8 us.
+// Tried and dropped: ONE chunk loop that branches between the 256- and the 128-column body (the compiler kept both bodies' views of
+// the ring: 612 registers at 96 rows, spills and vmcnt(0) waits inside the k loop -> a loop per kind over a host-built chunk
+// list); bias / scales by global loads at mid-chunk (64 registers through the k loop -> LDS tables); 64-bit addresses for the second
+// staging (96 registers held across the chunk loop -> buffer loads with one offset per lane).
+constexpr int kMaxProjGroups = 8;
+struct ProjGroup {
+    const u32x4 *w;
+    const float *bias;
+    float *y;
+    int N, cbase;   // cbase: the group's first entry in the block's bias / scale tables (the padded widths before it)
+};
+struct ProjGroups {
+    ProjGroup g[kMaxProjGroups];   // the groups without add_x2 first
+    int ng, nplain;                // nplain: how many of them take x alone
+    int ncols;                     // the padded widths of all groups together
+    // the chunks in the order they run: group | first column | kind as `gi << 16 | half << 15 | col0 / 128`.  Per staging phase
+    // (x; x + x2) the 256-column chunks of all its groups come first, then the 128-column ones: each kind has a loop of its own
+    // (one loop that branches between the two bodies per chunk made the compiler keep both bodies' views of the weight ring alive:
+    // 612 registers instead of 396 at 96 rows, spills and vmcnt(0) waits inside the k loop)
+    int nchunk[2][2];              // [phase][half]
+    int chunk[32];
+};
+constexpr int kMaxProjCols = 4096;   // ... which the LDS tables hold (2 x 16 KB at most); at most 32 chunks of 128 columns
+struct ChunkW {   // the calling wave's part of a chunk's weight stream: fragment (unit u, slot a, piece p) at base[((u us) + (a as) + p) 64]
+    const u32x4 *base;
+    int us, as;
+    bool half;
+};
+
+// the block's rows of x [+ x2] -> LDS as their 16-bit pieces, as stage_rows; through buffer resources over the M rows (rows past M
+// read zeros and are never stored): one 32-bit offset per lane and a scalar per load instead of a 64-bit address per load, which
+// the compiler otherwise keeps in registers across the whole chunk loop for the second staging
+template <int SP, int TI, bool ADD>
+__device__ __forceinline__ void stage_rows_sum(const __amdgpu_buffer_rsrc_t xrs, const __amdgpu_buffer_rsrc_t x2rs, int m0, unsigned short *sX, int tid)
+{
+    using G = Geo<256>;
+    constexpr int D = 256, C4 = D / 4, NV = TI * 32 * C4 / G::NT, RPI = G::NT / C4;   // float4 per thread; rows per pass of the block
+    static_assert(G::NT % C4 == 0, "a pass of the block covers whole rows");
+    const int row0 = tid / C4, c4 = tid - row0 * C4;
+    const unsigned voff = (unsigned)((m0 + row0) * D + c4 * 4) * 4u;
+    f32x4 xr[NV], xr2[ADD ? NV : 1];
+#pragma unroll
+    for (int it = 0; it < NV; ++it) {
+        xr[it] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xrs, voff, (unsigned)(it * RPI * D * 4), 0));
+        if constexpr (ADD) xr2[it] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(x2rs, voff, (unsigned)(it * RPI * D * 4), 0));
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int it = 0; it < NV; ++it) {
+        f32x4 xv = xr[it];
+        if constexpr (ADD) xv += xr2[it];   // rounded to fp32, then split: what the separate add + projection compute
+        u32x2 pc[Split<SP>::NA];
+        split4<SP>(xv, pc);
+#pragma unroll
+        for (int p = 0; p < Split<SP>::NA; ++p) *reinterpret_cast<u32x2 *>(&sX[(p * TI * 32 + it * RPI + row0) * G::XS + c4 * 4]) = pc[p];
+    }
+}
+
+template <int SP, int TI>
+__global__ void __launch_bounds__(256, (linln_min_blocks(256, TI)))
+linear_groups_kernel(const float *__restrict__ X, const float *__restrict__ X2, int M, const ProjGroups pg)
+{
+    using G = Geo<256>;
+    constexpr int BM = TI * 32, XS = G::XS, KQ = G::KQ1, NA = Split<SP>::NA, NB = Split<SP>::NB, US = 2 * NB;
+    constexpr bool F16 = Split<SP>::F16;
+    constexpr int RING = linln_ring(TI), AHEAD = RING - 2;
+    static_assert(KQ % RING == 0 && (KQ / 2) % RING == 0 && AHEAD <= KQ / 2, "a chunk starts at ring slot 0");
+    extern __shared__ __attribute__((aligned(16))) unsigned short s_f[];
+    unsigned short *const sX = s_f;   // [NA][BM][XS]
+    float *const sBias = reinterpret_cast<float *>(s_f + NA * BM * XS);   // [ncols]: bias (0 where there is none, and in the padding)
+    float *const sScale = sBias + pg.ncols;                                // [ncols]: fp16 scheme: r_n of the packed images
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int m0 = blockIdx.x * BM;
+    const int frow = lane & 31, xoff = frow * XS + (lane >> 5) * 8;
+
+    auto chunk_of = [&](int code) {
+        const ProjGroup &g = pg.g[code >> 16];
+        const int col0 = (code & 0x7fff) * 128;
+        ChunkW c;
+        c.half = (code >> 15) & 1;
+        const int tile = (col0 >> 5) + (c.half ? wave : 2 * wave);   // < the image's padded tile count: col0 % 128 == 0, padding to 256
+        c.base = g.w + (size_t)tile * (KQ * NB * 64) + lane;
+        c.us = c.half ? 2 * NB : NB;
+        c.as = c.half ? NB : KQ * NB;
+        return c;
+    };
+    u32x4 ring[RING][US];
+    auto load_unit = [&](const ChunkW &c, auto uc, u32x4 (&dst)[US]) {
+        constexpr int u = decltype(uc)::value;
+        const u32x4 *p0 = c.base + (size_t)(u * c.us) * 64;
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int p = 0; p < NB; ++p) dst[a * NB + p] = p0[(size_t)(a * c.as + p) * 64];
+    };
+    u32x4 xf[2][TI][NA];   // [k-step parity][row tile][piece]: the fragments of step st + 1 are read before the MFMAs of st
+    auto read_x = [&](auto stc) {
+        constexpr int st = decltype(stc)::value;
+#pragma unroll
+        for (int i = 0; i < TI; ++i)
+#pragma unroll
+            for (int p = 0; p < NA; ++p)
+                xf[st & 1][i][p] = *reinterpret_cast<const u32x4 *>(&sX[(p * BM + i * 32) * XS + xoff + st * 16]);
+    };
+
+    // one chunk: HALF ? 128 columns, one tile per wave : 256 columns, two tiles per wave
+    auto run_chunk = [&](auto halfc, const ChunkW &cur, const ChunkW &nxt, int code) {
+        constexpr bool HALF = decltype(halfc)::value;
+        constexpr int TJ = HALF ? 1 : 2, UNITS = HALF ? KQ / 2 : KQ;
+        const ProjGroup &g = pg.g[code >> 16];
+        const int col0 = (code & 0x7fff) * 128;
+        const int N = g.N;
+        const int wcol = col0 + wave * (32 * TJ);   // first column of the wave's tiles
+        f32x16 acc[TI][TJ];
+#pragma unroll
+        for (int i = 0; i < TI; ++i)
+#pragma unroll
+            for (int j = 0; j < TJ; ++j)
+#pragma unroll
+                for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+        read_x(std::integral_constant<int, 0>{});
+        static_for<KQ>([&](auto stc) {
+            constexpr int st = decltype(stc)::value;
+            constexpr int u = HALF ? st / 2 : st;   // the weight unit this k-step consumes
+            if constexpr (!HALF || (st & 1) == 0) {
+                constexpr int ahead = u + AHEAD;
+                if constexpr (ahead < UNITS) load_unit(cur, std::integral_constant<int, ahead>{}, ring[ahead % RING]);
+                else load_unit(nxt, std::integral_constant<int, ahead - UNITS>{}, ring[ahead % RING]);
+            }
+            if constexpr (st + 1 < KQ) read_x(std::integral_constant<int, st + 1>{});
+            __builtin_amdgcn_sched_barrier(0);   // loads and reads stay at the head of the step (see linear_stream.hip)
+            const u32x4 (&cu)[US] = ring[u % RING];
+            u32x4 wf[TJ][NB];
+#pragma unroll
+            for (int j = 0; j < TJ; ++j)
+#pragma unroll
+                for (int p = 0; p < NB; ++p) wf[j][p] = cu[(HALF ? (st & 1) : j) * NB + p];
+            mfma_tiles<SP, TI, TJ, false>(acc, xf[st & 1], wf);
+        });
+        // epilogue: transposed tiles (lane -> row m0 + 32 i + (lane & 31); registers 4 q .. 4 q + 3 of tile j -> columns wcol + 32 j +
+        // 8 q + 4 (lane >> 5) + 0..3); rows >= M fall outside the resource, and so does a whole tile of the image's padding (no records)
+        const unsigned ybytes = (unsigned)((size_t)M * N * 4);
+#pragma unroll
+        for (int j = 0; j < TJ; ++j) {
+            const __amdgpu_buffer_rsrc_t yrs = __builtin_amdgcn_make_buffer_rsrc(g.y, 0, wcol + 32 * j < N ? ybytes : 0u, 0x00020000);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int col = wcol + 32 * j + 8 * q + 4 * (lane >> 5);
+                const f32x4 bv = *reinterpret_cast<const f32x4 *>(sBias + g.cbase + col);
+                f32x4 rv = {1.f, 1.f, 1.f, 1.f};
+                if constexpr (F16) rv = *reinterpret_cast<const f32x4 *>(sScale + g.cbase + col);
+#pragma unroll
+                for (int i = 0; i < TI; ++i) {
+                    f32x4 v;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] = F16 ? __builtin_fmaf(acc[i][j][4 * q + e], rv[e], bv[e]) : acc[i][j][4 * q + e] + bv[e];
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), yrs,
+                                                           (unsigned)((m0 + i * 32 + frow) * N + col) * 4u, 0, tfm::kStoreAux);
+                }
+            }
+        }
+    };
+
+    const int total = pg.nchunk[0][0] + pg.nchunk[0][1] + pg.nchunk[1][0] + pg.nchunk[1][1];
+    int ci = 0;
+    ChunkW cur = chunk_of(pg.chunk[0]);
+    static_for<AHEAD>([&](auto uc) { load_unit(cur, uc, ring[decltype(uc)::value]); });   // the first units first (they have the longest way)
+    __builtin_amdgcn_sched_barrier(0);
+    const unsigned xbytes = (unsigned)((size_t)M * 256 * 4);
+    const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(X), 0, xbytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t x2rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(X2 ? X2 : X), 0, xbytes, 0x00020000);
+    for (int gq = 0; gq < pg.ng; ++gq) {   // the tables: 4 columns per thread and pass; the barrier behind the staging covers them
+        const ProjGroup &g = pg.g[gq];
+        const int npad = (g.N + 255) / 256 * 256;
+        const float *const r = reinterpret_cast<const float *>(g.w + (size_t)(npad / 32) * KQ * NB * 64);   // fp16 scheme: see ffn_fused_kernel
+        const __amdgpu_buffer_rsrc_t brs =
+            __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(g.bias ? g.bias : X), 0, g.bias ? (unsigned)g.N * 4u : 0u, 0x00020000);
+        for (int c = tid * 4; c < npad; c += 4 * G::NT) {
+            *reinterpret_cast<f32x4 *>(sBias + g.cbase + c) = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(brs, (unsigned)c * 4u, 0, 0));
+            if constexpr (F16) *reinterpret_cast<f32x4 *>(sScale + g.cbase + c) = *reinterpret_cast<const f32x4 *>(r + c);
+        }
+    }
+    if (pg.nplain == 0) stage_rows_sum<SP, TI, true>(xrs, x2rs, m0, sX, tid);
+    else stage_rows_sum<SP, TI, false>(xrs, x2rs, m0, sX, tid);
+    __syncthreads();
+#pragma unroll 1
+    for (int ph = 0; ph < 2; ++ph) {
+        if (ph == 1 && pg.nplain > 0 && pg.nplain < pg.ng) {   // the groups of x + x2 begin
+            __syncthreads();   // every wave is past its last read of the x tile
+            stage_rows_sum<SP, TI, true>(xrs, x2rs, m0, sX, tid);
+            __syncthreads();
+        }
+#pragma unroll 1
+        for (int k = 0; k < pg.nchunk[ph][0]; ++k, ++ci) {
+            const ChunkW nxt = chunk_of(pg.chunk[min(ci + 1, total - 1)]);   // after the last chunk: a harmless reload
+            run_chunk(std::false_type{}, cur, nxt, pg.chunk[ci]);
+            cur = nxt;
+        }
+#pragma unroll 1
+        for (int k = 0; k < pg.nchunk[ph][1]; ++k, ++ci) {
+            const ChunkW nxt = chunk_of(pg.chunk[min(ci + 1, total - 1)]);
+            run_chunk(std::true_type{}, cur, nxt, pg.chunk[ci]);
+            cur = nxt;
+        }
+    }
+}
+
+template <int SP, int TI>
+int launch_groups(const float *x, const float *x2, int M, const ProjGroups &pg, hipStream_t s)
+{
+    constexpr size_t tile = linln_lds_bytes<256>(TI, Split<SP>::NA), lds_max = tile + 2 * 4 * kMaxProjCols;
+    static_assert(lds_max <= 160 * 1024, "the activation tile and the tables do not fit the LDS of a CU");
+    const size_t lds = tile + 2 * 4 * (size_t)pg.ncols;
+    const void *fn = (const void *)&linear_groups_kernel<SP, TI>;
+    if (lds_max > 64 * 1024) {
+        static std::atomic<unsigned> raised;   // bit per device
+        int dev = 0;
+        (void)hipGetDevice(&dev);
+        if (dev >= 32 || !(raised.load() & (1u << dev))) {
+            if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max) != hipSuccess) return TF_MSDA_ERR_LAUNCH;
+            if (dev < 32) raised.fetch_or(1u << dev);
+        }
+    }
+    const int blocks = (M + 32 * TI - 1) / (32 * TI);
+    void *argv[] = {(void *)&x, (void *)&x2, (void *)&M, (void *)&pg};
+    return hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(256), argv, lds, s) == hipSuccess ? TF_MSDA_OK : TF_MSDA_ERR_LAUNCH;
+}
+
 }  // namespace
+
+extern "C" int tf_linear_groups_f32(const float *x, const float *x2, const tf_proj_group *groups, int ngroups, int64_t M, int K, int terms,
+                                    void *stream)
+{
+    if (!x || !groups) return TF_MSDA_ERR_NULL_POINTER;
+    if (ngroups < 1 || ngroups > kMaxProjGroups) return TF_MSDA_ERR_BAD_DIMS;
+    for (int i = 0; i < ngroups; ++i)
+        if (!groups[i].w_packed || !groups[i].y || (groups[i].add_x2 && !x2)) return TF_MSDA_ERR_NULL_POINTER;
+    const int sp = split_scheme(terms);
+    if (M <= 0 || K != 256 || sp == 0 || (M + 128) * (int64_t)K * 4 > 0xFFFFFFFFLL) return TF_MSDA_ERR_BAD_DIMS;   // (hidden 288: not built, the caller keeps the separate launches)
+    uintptr_t al = reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(x2);
+    ProjGroups pg{};
+    for (int pass = 0; pass < 2; ++pass)   // the groups of x alone first, each kind in the caller's order
+        for (int i = 0; i < ngroups; ++i) {
+            const tf_proj_group &g = groups[i];
+            if ((g.add_x2 != 0) != (pass == 1)) continue;
+            if (g.N <= 0 || (g.N % 32) != 0 || (M + 128) * (int64_t)g.N * 4 > 0xFFFFFFFFLL) return TF_MSDA_ERR_BAD_DIMS;   // 32-bit buffer offsets
+            al |= reinterpret_cast<uintptr_t>(g.w_packed) | reinterpret_cast<uintptr_t>(g.bias) | reinterpret_cast<uintptr_t>(g.y);
+            pg.g[pg.ng++] = ProjGroup{static_cast<const u32x4 *>(g.w_packed), g.bias, g.y, g.N, pg.ncols};
+            pg.ncols += (g.N + 255) / 256 * 256;
+            if (pass == 0) pg.nplain = pg.ng;
+        }
+    if ((al & 15) || pg.ncols > kMaxProjCols) return TF_MSDA_ERR_BAD_DIMS;
+    int nc = 0;
+    for (int ph = 0; ph < 2; ++ph)
+        for (int half = 0; half < 2; ++half)
+            for (int gi = ph ? pg.nplain : 0; gi < (ph ? pg.ng : pg.nplain); ++gi) {
+                const int N = pg.g[gi].N, full_end = N / 256 * 256;
+                for (int col0 = half ? full_end : 0; col0 < (half ? N : full_end); col0 += half ? 128 : 256) {
+                    pg.chunk[nc++] = gi << 16 | half << 15 | col0 / 128;
+                    ++pg.nchunk[ph][half];
+                }
+            }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // rows per block.  Three stored pieces: 32 (the only geometry built, as dispatch_linln prefers it).  Two: 96 from 4096 rows on,
+    // 32 below -- the threshold of the other fused routes, NOT a measured crossover: only 22 223 rows were timed (there 32 / 64 /
+    // 96 rows lie within 10 % of each other), and at 4096 rows 96-row blocks are 43 blocks on 256 CUs.  Option "groups_ti" forces it.
+    if (sp == 3) return launch_groups<3, 1>(x, x2, (int)M, pg, s);
+    const int forced = g_groups_ti.load(std::memory_order_relaxed);
+    switch (forced ? forced : (M < 4096 ? 1 : 3)) {
+    case 1: return launch_groups<16, 1>(x, x2, (int)M, pg, s);
+    case 2: return launch_groups<16, 2>(x, x2, (int)M, pg, s);
+    default: return launch_groups<16, 3>(x, x2, (int)M, pg, s);
+    }
+}
 
 extern "C" int tf_linear_res_ln_f32(const float *x, const void *w_packed, const float *bias, const float *residual,
                                     const float *ln_weight, const float *ln_bias, float ln_eps, float *y, int64_t M, int K, int N,

@@ -2288,6 +2288,7 @@ int tf_msda_set_option(const char *name, int value)
     if (strcmp(name, "ffn_ti") == 0) return ffn_set_ti(value);
     if (strcmp(name, "ffn_tail_split") == 0) return ffn_set_tail_split(value);
     if (strcmp(name, "linln_ti") == 0) return linln_set_ti(value);
+    if (strcmp(name, "groups_ti") == 0) return groups_set_ti(value);
     if (strcmp(name, "linear_stream_ti") == 0) return linear_stream_set_ti(value);
     if (strcmp(name, "conv_halo") == 0) return conv_halo_set(value);
     if (strcmp(name, "linear_dma") == 0) return linear_dma_set(value);

@@ -497,10 +497,11 @@ class DeformableTransformerDecoderLayer(nn.Module):
         return mha.out_proj(o.transpose(1, 2).reshape(n, lq, E)), False
 
     def forward(self, tgt, query_pos, reference_points, src, src_spatial_shapes,
-                src_padding_mask=None, query_attn_mask=None, filler_key_mask=None):
+                src_padding_mask=None, query_attn_mask=None, filler_key_mask=None, src_value=None):
         """filler_key_mask [N, Lq] (True = ignore as a KEY of the self-attention only): marks filler track queries
         that GraphedDetector appends to reach a bucketed query count; their own outputs are dropped by the caller, so
-        nothing else needs to know about them (the cross-attention is per query)."""
+        nothing else needs to know about them (the cross-attention is per query).
+        src_value (inference only): cross_attn.value_proj(src), computed by the decoder for all its layers in one launch."""
         # self attention among the (track + object) queries
         key_mask = query_attn_mask if query_attn_mask is not None else filler_key_mask
         if _inference(self) and tgt.is_cuda and self.self_attn.in_proj_weight is not None:
@@ -521,10 +522,10 @@ class DeformableTransformerDecoderLayer(nn.Module):
             else (self.with_pos_embed(tgt, query_pos), None)
         if inf and fused.linear_ln_fused_enabled():   # opt-in, as in the encoder layer
             tgt = self.cross_attn(cq, reference_points, src, src_spatial_shapes, src_padding_mask, query_attn_mask,
-                                  residual_norm=(tgt, self.norm1), query_pos=cq_pos)
+                                  residual_norm=(tgt, self.norm1), query_pos=cq_pos, value=src_value)
             return self.forward_ffn(tgt)
         tgt2 = self.cross_attn(cq, reference_points, src, src_spatial_shapes, src_padding_mask, query_attn_mask,
-                               query_pos=cq_pos)
+                               query_pos=cq_pos, value=src_value)
         tgt = fused.residual_norm(tgt, self.dropout1(tgt2), self.norm1, _inference(self))
         return self.forward_ffn(tgt)
 
@@ -545,6 +546,16 @@ class DeformableTransformerDecoder(nn.Module):
         intermediate = []
         intermediate_reference_points = []
         unit = getattr(src_valid_ratios, "_tf_unit", False)   # all-valid masks: the ratios are the cached tensor of ones
+        # inference: every layer's cross-attention projects the SAME memory with its own value_proj -- one launch for all of them
+        # (fused.linear_groups, up to 8 weights per launch); None: each layer projects for itself, as before
+        src_values = [None] * len(self.layers)
+        if (fused.proj_groups_enabled("dec") and src.is_cuda and not torch.is_grad_enabled()
+                and all(_inference(layer) and _inference(layer.cross_attn) for layer in self.layers)):
+            for a in range(0, len(self.layers), 8):
+                projs = [layer.cross_attn.value_proj for layer in self.layers[a:a + 8]]
+                ys = fused.linear_groups(src, None, [(p.weight, p.bias, False) for p in projs])
+                if ys is not None:
+                    src_values[a:a + len(ys)] = ys
         for lid, layer in enumerate(self.layers):
             if unit:
                 # x * 1.0 is x: the reference's concatenation + multiplication (deformable_transformer.py:343-348) are a broadcast view
@@ -556,7 +567,7 @@ class DeformableTransformerDecoder(nn.Module):
                 assert reference_points.shape[-1] == 2
                 reference_points_input = reference_points[:, :, None] * src_valid_ratios[:, None]
             output = layer(output, query_pos, reference_points_input, src, src_spatial_shapes,
-                           src_padding_mask, query_attn_mask, filler_key_mask)
+                           src_padding_mask, query_attn_mask, filler_key_mask, src_value=src_values[lid])
 
             if self.bbox_embed is not None:  # iterative bounding box refinement
                 tmp = self.bbox_embed[lid](output)

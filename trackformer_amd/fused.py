@@ -695,6 +695,102 @@ def linear_add(x, x2, weight, bias=None, rows=None):
     return y.view(*x.shape[:-1], N)
 
 
+# Several projections of the same rows in ONE launch (tf_linear_groups_f32, csrc/ffn_fused.hip): the token tile is fetched and split
+# once per workgroup instead of once per launch and 128-column block.  Bit-identical to linear() / linear_add() per group.  Two
+# callers, each with its own default (profiles/proj_groups_bench.json): the encoder layer's value + query
+# projections ("enc") and the six decoder layers' cross-attention value projections of the encoder memory ("dec").
+# TF_PROJ_GROUPS=0 / set_proj_groups(False) switches both off, TF_PROJ_GROUPS=1 both on, TF_PROJ_GROUPS=enc | dec one of them.
+def _parse_proj_groups(v):
+    v = str(v).strip().lower()
+    if v in ("", "0", "off", "false"):
+        return frozenset()
+    if v in ("1", "on", "true", "all"):
+        return frozenset(("enc", "dec"))
+    routes = frozenset(t.strip() for t in v.split(",") if t.strip())
+    if not routes <= {"enc", "dec"}:
+        raise ValueError("TF_PROJ_GROUPS: 0, 1 or a comma-separated subset of enc,dec")
+    return routes
+
+
+_PROJ_GROUPS_DEFAULT = "enc,dec"
+_proj_groups = _parse_proj_groups(os.environ.get("TF_PROJ_GROUPS", _PROJ_GROUPS_DEFAULT))
+_PROJ_GROUPS_MIN_ROWS = int(os.environ.get("TF_PROJ_GROUPS_MIN_ROWS", "4096"))   # the other fused routes' threshold; only 22 223 rows were measured
+
+
+def proj_groups_enabled(route=None):
+    """Whether the grouped projection launch is on for `route` ("enc" / "dec"; None: for any)."""
+    return bool(_proj_groups) if route is None else route in _proj_groups
+
+
+def set_proj_groups(on):
+    """Switch the grouped projection launches (process-wide): False / True for both callers, or "enc" / "dec" / "enc,dec" / an
+    iterable of those names; returns the previous setting (a frozenset, accepted back)."""
+    global _proj_groups
+    if isinstance(on, (set, frozenset, list, tuple)):
+        new = _parse_proj_groups(",".join(sorted(on)))
+    elif isinstance(on, str):
+        new = _parse_proj_groups(on)
+    else:
+        new = _parse_proj_groups("1" if on else "0")
+    prev, _proj_groups = _proj_groups, new
+    return _switched(prev, _proj_groups)
+
+
+def set_proj_groups_min_rows(n):
+    """Rows from which linear_groups() applies (process-wide); returns the previous value."""
+    global _PROJ_GROUPS_MIN_ROWS
+    prev, _PROJ_GROUPS_MIN_ROWS = _PROJ_GROUPS_MIN_ROWS, int(n)
+    return _switched(prev, _PROJ_GROUPS_MIN_ROWS)
+
+
+def linear_groups(x, x2, groups):
+    """[(x + x2 if add else x) @ weight^T + bias for (weight, bias, add) in groups] through ONE tf_linear_groups_f32 launch; None when
+    it does not apply (the caller keeps linear() / linear_add()).  x [..., 256] fp32 on the GPU, x2 like x (or None if no group
+    adds); weights: persistent [N, 256] fp32 tensors (their packed images are _packed_weight's, cached on them), N % 32 == 0."""
+    if not (_split_linear and x.is_cuda and x.dtype == torch.float32 and 1 <= len(groups) <= 8 and x.numel()):
+        return None
+    if _split_terms == 16 and (_n_six_term_routes or debug_checks_active()):
+        return None   # per-layer six-term routes, the range audit and the finite check live on the per-layer wrappers
+    K = x.shape[-1]
+    if K != 256:
+        return None
+    any_add = any(add for _w, _b, add in groups)
+    if any_add and (x2 is None or x2.dtype != torch.float32 or x2.shape != x.shape or x2.device != x.device):
+        return None
+    a = x.reshape(-1, K)
+    a = a if a.is_contiguous() else a.contiguous()
+    M = a.shape[0]
+    if M < _PROJ_GROUPS_MIN_ROWS or (M + 128) * K * 4 > 0xFFFFFFFF:
+        return None
+    b = None
+    if any_add:
+        b = x2.reshape(-1, K)
+        b = b if b.is_contiguous() else b.contiguous()
+    if (a.data_ptr() | _ptr(b)) & 15:
+        return None
+    cols = 0
+    for w, bias, _add in groups:
+        if not (w.dtype == torch.float32 and w.dim() == 2 and w.is_contiguous() and w.device == x.device and w.shape[1] == K
+                and w.shape[0] % 32 == 0 and (M + 128) * w.shape[0] * 4 <= 0xFFFFFFFF):
+            return None
+        if bias is not None and not (_param_ok(bias, x) and bias.numel() == w.shape[0]):
+            return None
+        cols += (w.shape[0] + 255) // 256 * 256
+    if cols > 4096:
+        return None
+    packed = [_packed_weight(w, None) for w, _b, _add in groups]
+    if any(p is None for p in packed):   # (capturing while an image is missing: this call takes the separate kernels)
+        return None
+    descs = (_cabi.ProjGroup * len(groups))()
+    with torch.cuda.device(x.device):
+        ys = [torch.empty((M, w.shape[0]), dtype=torch.float32, device=x.device) for w, _b, _add in groups]
+        for d, (w, bias, add), p, y in zip(descs, groups, packed, ys):
+            d.w_packed, d.bias, d.y, d.N, d.add_x2 = p.data_ptr(), (bias.data_ptr() if bias is not None else None), y.data_ptr(), w.shape[0], int(bool(add))
+        rc = _cabi.lib().tf_linear_groups_f32(a.data_ptr(), _ptr(b) or None, descs, len(groups), M, K, _terms(), _stream(x.device))
+    _cabi.check(rc, "tf_linear_groups_f32")
+    return [y.view(*x.shape[:-1], y.shape[1]) for y in ys]
+
+
 def conv3x3(x, w_taps, bias, relu, stride):
     """3 x 3 convolution (padding 1) -- or, with a [Cout, Cin] weight, a strided 1 x 1 convolution without padding -- of a
     channels_last fp32 GPU activation through tf_conv3x3_split_f32 / tf_conv1x1_strided_split_f32.

@@ -481,24 +481,26 @@ class MSDeformAttn(nn.Module):
             constant_(self.output_proj.bias, 0.)
 
     def forward(self, query, reference_points, input_flatten, input_spatial_shapes,
-                input_padding_mask=None, query_attn_mask=None, residual_norm=None, query_pos=None):
+                input_padding_mask=None, query_attn_mask=None, residual_norm=None, query_pos=None, value=None):
         """query[N,Lq,C], reference_points[N,Lq,L,2|4] in [0,1], input_flatten[N,S,C],
         input_spatial_shapes[L,2] (H_l,W_l), input_padding_mask[N,S] (True = padding)
         -> [N,Lq,C]   (modules/ms_deform_attn.py:49-89).
         residual_norm = (residual, nn.LayerNorm) (an extension used by the inference path of the layers): return
         norm(residual + attention output) instead -- the output projection, the add and the norm can then be one launch.
-        query_pos (extension, inference path): the query is `query + query_pos`; the add can then ride in the projection."""
+        query_pos (extension, inference path): the query is `query + query_pos`; the add can then ride in the projection.
+        value (extension, inference path): value_proj(input_flatten) [N, S, C], computed by the caller (the decoder projects the
+        memory for all its layers in one launch); the padding mask is still applied here."""
         if residual_norm is not None:
             out = self._forward(query, reference_points, input_flatten, input_spatial_shapes, input_padding_mask,
-                                query_attn_mask, residual_norm, query_pos)
+                                query_attn_mask, residual_norm, query_pos, value)
             if isinstance(out, _Normed):
                 return out.value
             return fused.residual_norm(residual_norm[0], out, residual_norm[1], True)
         return self._forward(query, reference_points, input_flatten, input_spatial_shapes, input_padding_mask, query_attn_mask,
-                             None, query_pos)
+                             None, query_pos, value)
 
     def _forward(self, query, reference_points, input_flatten, input_spatial_shapes, input_padding_mask, query_attn_mask,
-                 residual_norm, query_pos=None):
+                 residual_norm, query_pos=None, value=None):
         N, Len_q, _ = query.shape
         N, Len_in, _ = input_flatten.shape
         hs = _host_shapes_of(input_spatial_shapes)
@@ -510,19 +512,29 @@ class MSDeformAttn(nn.Module):
 
         M, L, P = self.n_heads, self.n_levels, self.n_points
         inference = not self.training and not torch.is_grad_enabled()
-        value = fused.module_linear(self.value_proj, input_flatten, inference)
+        # what the fused inference entry needs, apart from an fp32 device `value` (checked where it is used; linear_groups checks its input)
+        fused_inference = (FUSED_INFERENCE and hs is not None and query_attn_mask is None and inference
+                           and reference_points.shape[-1] in (2, 4) and (self.d_model // M) % 4 == 0 and P in (1, 2, 4, 8))
+        qproj = None
+        if value is not None and not inference:
+            raise ValueError("MSDeformAttn: a precomputed `value` is an inference-path extension")
+        if (value is None and fused_inference and query_pos is not None and input_flatten is query and fused.proj_groups_enabled("enc")
+                and fused.pos_add_fused_enabled()):
+            # the encoder layer: value_proj(src) and the query projections of src + pos share their rows: one launch
+            w, b = self._cat_proj.get(self)
+            ys = fused.linear_groups(query, query_pos, [(self.value_proj.weight, self.value_proj.bias, False), (w, b, True)])
+            if ys is not None:
+                value, qproj = ys
+        if value is None:
+            value = fused.module_linear(self.value_proj, input_flatten, inference)
         if input_padding_mask is not None:
             value = value.masked_fill(input_padding_mask[..., None], float(0))
         value = value.view(N, Len_in, M, self.d_model // M)
 
-        if (FUSED_INFERENCE and hs is not None and query_attn_mask is None and value.is_cuda
-                and value.dtype == torch.float32 and not self.training
-                and not torch.is_grad_enabled() and reference_points.shape[-1] in (2, 4)
-                and (self.d_model // M) % 4 == 0 and P in (1, 2, 4, 8)):
+        if fused_inference and value.is_cuda and value.dtype == torch.float32:
             # inference: one GEMM for both query projections, prologue arithmetic inside the kernel
             w, b = self._cat_proj.get(self)
-            qproj = None
-            if query_pos is not None:   # opt-in: the positional add inside the projection GEMM
+            if qproj is None and query_pos is not None:   # opt-in: the positional add inside the projection GEMM
                 qproj = fused.linear_add(query, query_pos, w, b)
                 if qproj is None:
                     query = query + query_pos
