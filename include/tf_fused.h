@@ -320,6 +320,44 @@ int tf_linear_dgrad_packed_f32(const float *dy, const float *dy_scale2, const vo
                                int terms, void *stream);
 
 /*
+ * THE BACKWARD OF THE RESIDUAL LAYERNORM  out = LayerNorm(x + res) gamma + beta  (trackformer_amd/csrc/layernorm_bwd.h; reference: the
+ * autograd of `src = src + dropout(src2); src = norm(src)` of models/deformable_transformer.py, fp32).  With z = x + res (z = x for
+ * res == NULL), mean / rstd = 1 / sqrt(var + eps) of the row, xh = (z - mean) rstd and g = gamma dy:
+ *     dz[r, :]  = rstd (g - mean_c(g) - xh mean_c(g xh))        dgamma[c] = sum_r dy[r, c] xh[r, c]        dbeta[c] = sum_r dy[r, c]
+ * dz is the gradient with respect to x AND to res: one tensor, written once.
+ *
+ *   tf_add_layernorm_train_f32   tf_add_layernorm_f32 that also saves stats[r] = (mean, rstd) [rows, 2], exactly the two fp32 values row r
+ *                                was normalised with.  The kernel and its arithmetic are those of tf_add_layernorm_f32: `out` is
+ *                                bit-identical to it on the same operands.  Nothing else is saved: the backward reads x and res again.
+ *   tf_add_layernorm_bwd_f32     one pass over the rows, one wave per row: z is formed again by the forward's single fp32 addition, xh
+ *                                from the saved statistics; mean_c by a butterfly over the wave; dz written once.  In the same pass
+ *                                every lane sums dy and dy xh of its own columns over the rows its wave walks.  The rows are cut into
+ *                                blocks by a rule of `rows` alone (16 rows per block up to 32 768 rows, ceil(rows / 2048) beyond: at most
+ *                                2048 blocks; never the grid, the CU count or the occupancy -- as the row blocks of
+ *                                tf_linear_grad_stats_f32); a block's four waves are added in wave order (rows w, w + 4, ... of the
+ *                                block in wave w, ascending) and the block writes one partial row [2, C] to `workspace`.  A second,
+ *                                small launch adds the partials: slice s = 0 .. 15 takes blocks s, s + 16, ... in that order, then the
+ *                                slices in the order 0, 1, ...  dz / dgamma / dbeta may each be NULL: without dgamma and dbeta the
+ *                                column sums are compiled out of the first launch, the second is skipped and workspace may be NULL.
+ *                                workspace: tf_add_layernorm_bwd_workspace_bytes(rows, C) = blocks . 2 C . 4 bytes.
+ * C % 4 == 0, C <= 4096, rows < 2^31; dy / x / res / gamma / dz / dgamma / dbeta / workspace 16-byte aligned, stats 8-byte aligned.  dz must
+ * not overlap an input.
+ * No atomics anywhere and every sum in a fixed order: each result is a pure function of the arguments -- bit-identical from call to
+ * call, on any stream and in a captured HIP graph.
+ * Non-finite operands: rows are independent in dz -- a NaN or an inf in row r of dy, x or res makes the elements of row r non-finite
+ * where the exact value is, and changes no bit of any other row; dgamma[c] and dbeta[c] are non-finite exactly when their exact sum is
+ * (a NaN in x[r, :] reaches every xh[r, c] through the row's mean, hence every dgamma[c]; a NaN in dy[r, c] reaches column c alone).
+ * Checked in this order, before any GPU work: NULL dy / x / gamma / stats (train: x / gamma / beta / out / stats) ->
+ * TF_MSDA_ERR_NULL_POINTER, dimensions / alignment -> TF_MSDA_ERR_BAD_DIMS, with dgamma or dbeta a workspace that is NULL, too small
+ * or misaligned -> TF_MSDA_ERR_WORKSPACE.  tf_add_layernorm_bwd_workspace_bytes returns -1 for dimensions the entry point rejects.
+ */
+int tf_add_layernorm_train_f32(const float *x, const float *res, const float *gamma, const float *beta, float *out, float *stats,
+                               int64_t rows, int C, float eps, void *stream);
+int64_t tf_add_layernorm_bwd_workspace_bytes(int64_t rows, int C);
+int tf_add_layernorm_bwd_f32(const float *dy, const float *x, const float *res, const float *gamma, const float *stats, float *dz,
+                             float *dgamma, float *dbeta, void *workspace, int64_t workspace_bytes, int64_t rows, int C, void *stream);
+
+/*
  * Convolution of a channels_last activation through the same kernel (an implicit GEMM over the output pixels; the weight
  * fragments streamed from L2, only the shifted input pixels pass LDS): ks = 3 (padding 1) or 1 (no padding), stride 1 or 2.
  *   x [nimg, hin, win, cin] NHWC fp32, below 3 GiB;  y [nimg, hout, wout, cout] NHWC, below 3 GiB;  cin % 64 == 0

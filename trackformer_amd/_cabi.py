@@ -66,6 +66,9 @@ EXPORTED_SYMBOLS = (
     "tf_linear_wgrad_workspace_bytes",
     "tf_linear_wgrad_split_f32",
     "tf_linear_dgrad_packed_f32",
+    "tf_add_layernorm_train_f32",
+    "tf_add_layernorm_bwd_workspace_bytes",
+    "tf_add_layernorm_bwd_f32",
     "tf_linear_split_add_f32",
     "tf_ffn_fused_f32",
     "tf_linear_res_ln_f32",
@@ -75,7 +78,7 @@ EXPORTED_SYMBOLS = (
     "tf_nms_host_f32",
 )
 
-ABI_VERSION = 6   # 6: tf_msda_fused_prologue / _backward_epilogue (5: tf_linear_grad_stats / wgrad / dgrad; 4: tf_msda_backward_det_* and TF_MSDA_ERR_WORKSPACE; 3: the split-product entry points take w_lo / w_scale / terms)
+ABI_VERSION = 7   # 7: tf_add_layernorm_train / _bwd (6: tf_msda_fused_prologue / _backward_epilogue; 5: tf_linear_grad_stats / wgrad / dgrad; 4: tf_msda_backward_det_* and TF_MSDA_ERR_WORKSPACE; 3: the split-product entry points take w_lo / w_scale / terms)
 
 _lib = None
 
@@ -208,6 +211,12 @@ def lib():
     L.tf_linear_wgrad_split_f32.argtypes = [vp, vp, vp, vp, vp, vp, i64, i64, ci, ci, ci, vp]
     L.tf_linear_dgrad_packed_f32.restype = ci
     L.tf_linear_dgrad_packed_f32.argtypes = [vp, vp, vp, vp, i64, ci, ci, ci, vp]
+    L.tf_add_layernorm_train_f32.restype = ci
+    L.tf_add_layernorm_train_f32.argtypes = [vp, vp, vp, vp, vp, vp, i64, ci, ctypes.c_float, vp]
+    L.tf_add_layernorm_bwd_workspace_bytes.restype = i64
+    L.tf_add_layernorm_bwd_workspace_bytes.argtypes = [i64, ci]
+    L.tf_add_layernorm_bwd_f32.restype = ci
+    L.tf_add_layernorm_bwd_f32.argtypes = [vp] * 9 + [i64, i64, ci, vp]
     L.tf_conv_packed_f32.restype = ci
     L.tf_conv_packed_f32.argtypes = [vp, vp, vp, vp, vp, vp] + [ci] * 10 + [vp]
     L.tf_mha_core_f32.restype = ci

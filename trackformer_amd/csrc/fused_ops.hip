@@ -16,6 +16,7 @@
 namespace {
 
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
+typedef float f32x2_t __attribute__((ext_vector_type(2)));
 
 // x += bias[channel] (+ residual) (ReLU), in place.  The residual / ReLU tests are template parameters and two grid strides
 // are processed per iteration with all of their loads issued first: the straightforward loop (one element per iteration, a
@@ -71,12 +72,14 @@ __device__ __forceinline__ float wave_sum(float v)
     return v;
 }
 
-// One wavefront per row; lane j owns float4 chunks j, j+64, ... of the row (kept in registers).
-template <int MAXCH>
+// One wavefront per row; lane j owns float4 chunks j, j+64, ... of the row (kept in registers).  STATS (the training entry,
+// tf_add_layernorm_train_f32): lane 0 also writes the (mean, rstd) the row was normalised with to stats[r] -- the arithmetic of
+// `out` is this one body either way.
+template <int MAXCH, bool STATS>
 __global__ void __launch_bounds__(256)
 add_layernorm_kernel(const float *__restrict__ x, const float *__restrict__ res,
                      const float *__restrict__ gamma, const float *__restrict__ beta,
-                     float *__restrict__ out, long long rows, int C, float eps)
+                     float *__restrict__ out, float *__restrict__ stats, long long rows, int C, float eps)
 {
     const int lane = threadIdx.x & 63;
     const int C4 = C >> 2;
@@ -97,7 +100,8 @@ add_layernorm_kernel(const float *__restrict__ x, const float *__restrict__ res,
                 s += (v[k].x + v[k].y) + (v[k].z + v[k].w);
             }
         }
-        const float mean = wave_sum(s) / (float)C;
+        const float tsum = wave_sum(s);
+        const float mean = tsum / (float)C;
         float sq = 0.f;
 #pragma unroll
         for (int k = 0; k < MAXCH; ++k) {
@@ -107,7 +111,8 @@ add_layernorm_kernel(const float *__restrict__ x, const float *__restrict__ res,
                 sq += (d.x * d.x + d.y * d.y) + (d.z * d.z + d.w * d.w);
             }
         }
-        const float rstd = rsqrtf(wave_sum(sq) / (float)C + eps);
+        const float tsq = wave_sum(sq);
+        const float rstd = rsqrtf(tsq / (float)C + eps);
         f32x4_t *orow = reinterpret_cast<f32x4_t *>(out + r * C);
 #pragma unroll
         for (int k = 0; k < MAXCH; ++k) {
@@ -118,10 +123,25 @@ add_layernorm_kernel(const float *__restrict__ x, const float *__restrict__ res,
                 tfm::stream_store(orow + j, (v[k] - mean) * rstd * g + b);
             }
         }
+        if constexpr (STATS) {
+            // the row's two statistics once more, from the wave's totals through a scalar register: the same operations on the same
+            // values (bit-identical to mean / rstd), but no second use of `mean` / `rstd` themselves -- one more user of those two changes
+            // how the compiler vectorises and contracts the row's arithmetic (add_layernorm_kernel<1, .>: v_mul + v_fmac became
+            // v_pk_mul + v_pk_add in the sum of squares), and `out` must keep the bits of the inference instantiation
+            const float us = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, tsum)));
+            const float uq = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, tsq)));
+            if (lane == 0) reinterpret_cast<f32x2_t *>(stats)[r] = f32x2_t{us / (float)C, rsqrtf(uq / (float)C + eps)};
+        }
     }
 }
 
 bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+}  // namespace
+
+#include "layernorm_bwd.h"
+
+namespace {
 
 // ---- GroupNorm over channels-innermost activations: x [N, HW, C] (the storage of a channels_last NCHW tensor, or a
 // token-major projection output), statistics per (image, group) over HW x (C / G) elements.  Two passes:
@@ -631,31 +651,48 @@ int tf_bias_act_f32(float *x, const float *bias, const float *residual, int64_t 
     return hipGetLastError() == hipSuccess ? TF_MSDA_OK : TF_MSDA_ERR_LAUNCH;
 }
 
-int tf_add_layernorm_f32(const float *x, const float *res, const float *gamma, const float *beta,
-                         float *out, int64_t rows, int C, float eps, void *stream)
+static int add_layernorm_impl(const float *x, const float *res, const float *gamma, const float *beta, float *out, float *stats,
+                              int64_t rows, int C, float eps, void *stream)
 {
-    if (!x || !gamma || !beta || !out) return TF_MSDA_ERR_NULL_POINTER;
     if (rows <= 0 || C <= 0 || (C & 3) || C > 4096) return TF_MSDA_ERR_BAD_DIMS;
     if (!aligned16(x) || !aligned16(gamma) || !aligned16(beta) || !aligned16(out) ||
-        (res && !aligned16(res)))
+        (res && !aligned16(res)) || (reinterpret_cast<uintptr_t>(stats) & 7))
         return TF_MSDA_ERR_BAD_DIMS;
     long long blocks = (rows + 3) / 4;   // 4 waves (rows) per 256-thread workgroup
     if (blocks > 256 * 16) blocks = 256 * 16;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int chunks = (C / 4 + 63) / 64;
-    if (chunks <= 1)
-        hipLaunchKernelGGL(add_layernorm_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, s, x, res,
-                           gamma, beta, out, (long long)rows, C, eps);
-    else if (chunks <= 2)
-        hipLaunchKernelGGL(add_layernorm_kernel<2>, dim3((unsigned)blocks), dim3(256), 0, s, x, res,
-                           gamma, beta, out, (long long)rows, C, eps);
-    else if (chunks <= 4)
-        hipLaunchKernelGGL(add_layernorm_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, s, x, res,
-                           gamma, beta, out, (long long)rows, C, eps);
-    else
-        hipLaunchKernelGGL(add_layernorm_kernel<16>, dim3((unsigned)blocks), dim3(256), 0, s, x, res,
-                           gamma, beta, out, (long long)rows, C, eps);
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, s, x, res, gamma, beta, out, stats, (long long)rows, C, eps);
+    };
+    if (stats) {
+        if (chunks <= 1) launch(add_layernorm_kernel<1, true>);
+        else if (chunks <= 2) launch(add_layernorm_kernel<2, true>);
+        else if (chunks <= 4) launch(add_layernorm_kernel<4, true>);
+        else launch(add_layernorm_kernel<16, true>);
+    } else {
+        if (chunks <= 1) launch(add_layernorm_kernel<1, false>);
+        else if (chunks <= 2) launch(add_layernorm_kernel<2, false>);
+        else if (chunks <= 4) launch(add_layernorm_kernel<4, false>);
+        else launch(add_layernorm_kernel<16, false>);
+    }
     return hipGetLastError() == hipSuccess ? TF_MSDA_OK : TF_MSDA_ERR_LAUNCH;
+}
+
+int tf_add_layernorm_f32(const float *x, const float *res, const float *gamma, const float *beta,
+                         float *out, int64_t rows, int C, float eps, void *stream)
+{
+    if (!x || !gamma || !beta || !out) return TF_MSDA_ERR_NULL_POINTER;
+    return add_layernorm_impl(x, res, gamma, beta, out, nullptr, rows, C, eps, stream);
+}
+
+int tf_add_layernorm_train_f32(const float *x, const float *res, const float *gamma, const float *beta, float *out, float *stats,
+                               int64_t rows, int C, float eps, void *stream)
+{
+    if (!x || !gamma || !beta || !out || !stats) return TF_MSDA_ERR_NULL_POINTER;
+    const int rc = add_layernorm_impl(x, res, gamma, beta, out, stats, rows, C, eps, stream);
+    if (rc == TF_MSDA_OK) tfm::note_kernel("add_layernorm_stats_f32");
+    return rc;
 }
 
 }  // extern "C"

@@ -123,9 +123,14 @@ def add_layernorm(x, res, norm):
 
 
 def residual_norm(x, res, norm, inference):
-    """norm(x + res): fused on the GPU inference path, plain PyTorch otherwise."""
+    """norm(x + res): fused on the GPU inference path; with gradients enabled and set_layernorm_training(True) the same kernel with the
+    library's own backward (layernorm_train); plain PyTorch otherwise."""
     if inference:
         y = add_layernorm(x, res, norm)
+        if y is not None:
+            return y
+    elif layernorm_train_route(x):
+        y = layernorm_train(x, res, norm)
         if y is not None:
             return y
     return norm(x + res)
@@ -1413,7 +1418,7 @@ conv3x3 = _ranged("conv3x3", lambda x, w_taps, *a, **k: (w_taps,), lambda x, *a,
 # TF_SPLIT_LINEAR_TRAIN=1 routes module_linear, the feed-forward block's first linear and the four projections of MSDeformAttn through
 # linear_train instead: the forward is linear() (bit-identical to the inference path), the backward the library's own input-gradient,
 # weight-gradient and bias-gradient kernels -- no float atomics, bit-identical from call to call.  NOT covered: convolutions,
-# nn.MultiheadAttention's internals, LayerNorm.  OFF by default: whether it is faster inside a training step is a measurement
+# nn.MultiheadAttention's internals (the residual + LayerNorm sites have a switch of their own: set_layernorm_training below).  OFF by default: whether it is faster inside a training step is a measurement
 # (tools/bench_linear_backward.py, profiles/linear_backward_bench.json), not a promise.
 _split_linear_train = None    # None: follow TF_SPLIT_LINEAR_TRAIN (unset: off)
 _train_counts = {"dgrad_own": 0, "dgrad_torch": 0, "wgrad_own": 0, "wgrad_torch": 0, "bias_own": 0, "bias_torch": 0}
@@ -1584,3 +1589,117 @@ def linear_train(x, weight, bias=None, relu=False):
         return _LinearTrain.apply(x, weight, bias, relu)
     except _NotApplicable:
         return None
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# THE TRAINING PATH OF THE RESIDUAL + LAYERNORM SITES (opt-in; include/tf_fused.h: THE BACKWARD OF THE RESIDUAL LAYERNORM;
+# csrc/layernorm_bwd.h).  With gradients enabled every residual_norm() site is norm(x + res): an ATen add that writes the sum, the
+# library's LayerNorm forward, its backward and its two-kernel gamma / beta reduction.  set_layernorm_training(True) /
+# TF_LAYERNORM_TRAIN=1 routes these sites through layernorm_train instead: the forward is the inference kernel (bit-identical to
+# add_layernorm) plus the rows' (mean, rstd), the backward one pass over the rows and a small column reduction -- no atomics,
+# bit-identical from call to call.  Dropout sits before the add and stays a torch op, so the route holds under dropout 0.1.  NOT
+# covered: GroupNorm, the LayerNorm epilogues of the fused inference kernels (linear_residual_norm, ffn), nn.MultiheadAttention's
+# internals.  OFF by default: whether it is faster inside a training step is a measurement (tools/bench_layernorm_train.py,
+# profiles/layernorm_train_bench.json), not a promise.
+_layernorm_train = None    # None: follow TF_LAYERNORM_TRAIN (unset: off)
+_layernorm_train_counts = {"own": 0, "torch": 0}
+
+
+def layernorm_training_enabled():
+    if _layernorm_train is not None:
+        return _layernorm_train
+    return os.environ.get("TF_LAYERNORM_TRAIN", "0") not in ("", "0")
+
+
+def set_layernorm_training(flag):
+    """Switch the training path of the residual + LayerNorm sites on or off (process-wide; None: follow TF_LAYERNORM_TRAIN again);
+    returns the previous setting."""
+    global _layernorm_train
+    prev = layernorm_training_enabled()
+    _layernorm_train = None if flag is None else bool(flag)
+    return _switched(prev, layernorm_training_enabled())
+
+
+def layernorm_train_route(x):
+    """A call with gradients enabled that layernorm_train takes: the switch is on and x is an fp32 tensor on the device."""
+    return layernorm_training_enabled() and torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.float32
+
+
+def layernorm_train_counts(reset=False):
+    """How many layernorm_train calls ran the library's own kernels ("own") and how many were declined ("torch": the caller kept
+    norm(x + res))."""
+    out = dict(_layernorm_train_counts)
+    if reset:
+        for k in _layernorm_train_counts:
+            _layernorm_train_counts[k] = 0
+    return out
+
+
+class _LayerNormTrain(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, res, weight, bias, eps):
+        C = x.shape[-1]
+        rows = x.numel() // C
+        with torch.cuda.device(x.device):
+            out = torch.empty_like(x)
+            stats = torch.empty((rows, 2), dtype=torch.float32, device=x.device)
+            rc = _cabi.lib().tf_add_layernorm_train_f32(x.data_ptr(), _ptr(res), weight.data_ptr(), bias.data_ptr(), out.data_ptr(),
+                                                        stats.data_ptr(), rows, C, float(eps), _stream(x.device))
+        _cabi.check(rc, "tf_add_layernorm_train_f32")
+        ctx.save_for_backward(x, res, weight, stats)   # what torch keeps for this chain: no sum, no normalised activation
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, res, weight, stats = ctx.saved_tensors
+        need_x, need_res, need_w, need_b = ctx.needs_input_grad[:4]
+        C = x.shape[-1]
+        rows = x.numel() // C
+        dy = dy if dy.is_contiguous() and not dy.data_ptr() & 15 else dy.clone(memory_format=torch.contiguous_format)
+        L = _cabi.lib()
+        dz = dw = db = None
+        with torch.cuda.device(x.device):
+            if need_x or need_res:
+                dz = torch.empty_like(x)
+            if need_w:
+                dw = torch.empty_like(weight)
+            if need_b:
+                db = torch.empty_like(weight)
+            nbytes = 0
+            ws = None
+            if need_w or need_b:
+                nbytes = int(L.tf_add_layernorm_bwd_workspace_bytes(rows, C))
+                if nbytes < 0:
+                    _cabi.check(-2, "tf_add_layernorm_bwd_f32")
+                ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+            if dz is not None or ws is not None:
+                rc = L.tf_add_layernorm_bwd_f32(dy.data_ptr(), x.data_ptr(), _ptr(res), weight.data_ptr(), stats.data_ptr(), _ptr(dz), _ptr(dw),
+                                                _ptr(db), _ptr(ws), nbytes, rows, C, _stream(x.device))
+                _cabi.check(rc, "tf_add_layernorm_bwd_f32")
+        return (dz if need_x else None), (dz if need_res else None), dw, db, None
+
+
+def layernorm_train(x, res, norm):
+    """norm(x + res) (res may be None) with the library's own backward: the forward IS the inference kernel (bit-identical to
+    add_layernorm) and saves x, res, norm.weight and the rows' (mean, rstd); the backward is tf_add_layernorm_bwd_f32
+    (include/tf_fused.h) and returns ONE tensor as the gradient of both x and res.  None -- the caller keeps norm(x + res) -- for
+    anything the kernels do not take: not fp32, not on the device, a non-contiguous x, C % 4 != 0 or C > 4096, no affine parameters,
+    misaligned pointers, a res of another shape / dtype / device.  A non-contiguous res of the right shape (the decoder's transposed
+    self-attention output) is copied first, as add_layernorm does on the inference path; the copy is a torch op and differentiable.
+    layernorm_train_counts() tells which way the calls went."""
+    ok = (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.numel() > 0 and x.data_ptr() % 16 == 0
+          and norm.elementwise_affine and norm.bias is not None and len(norm.normalized_shape) == 1)
+    if ok:
+        C = norm.normalized_shape[0]
+        ok = x.shape[-1] == C and C % 4 == 0 and C <= 4096 and _param_ok(norm.weight, x) and _param_ok(norm.bias, x)
+    if ok and res is not None:
+        ok = res.shape == x.shape and res.dtype == x.dtype and res.device == x.device
+        if ok and not res.is_contiguous():
+            res = res.contiguous()   # as add_layernorm: the decoder's self-attention output arrives transposed (a differentiable copy)
+        ok = ok and res.data_ptr() % 16 == 0
+    if not ok:
+        _layernorm_train_counts["torch"] += 1
+        return None
+    _layernorm_train_counts["own"] += 1
+    return _LayerNormTrain.apply(x, res, norm.weight, norm.bias, norm.eps)
