@@ -358,6 +358,58 @@ int tf_add_layernorm_bwd_f32(const float *dy, const float *x, const float *res, 
                              float *dgamma, float *dbeta, void *workspace, int64_t workspace_bytes, int64_t rows, int C, void *stream);
 
 /*
+ * THE SET CRITERION AND THE MATCHING COST  (trackformer_amd/csrc/criterion.h; reference: loss_labels_focal / loss_cardinality /
+ * loss_boxes of models/detr.py and the focal branch of models/matcher.py, fp32).  The decoder layers' predictions are stacked:
+ * logits [L, B, Q, C], boxes [L, B, Q, 4] (cxcywh), contiguous.  tgt_of int32 [L, B, Q] holds the GLOBAL index (into labels / tboxes, the
+ * images' targets concatenated) of the target matched to that prediction, or -1; a value outside [0, T) counts as -1 and no target is
+ * read for it.  labels int64 [T], tboxes [T, 4], tgt_len int32 [B] (targets per image).
+ *
+ *   tf_set_criterion_fwd_f32   one launch, one 256-thread workgroup per layer:
+ *                                losses[l] = (loss_ce, loss_bbox, loss_giou)   card[l] = mean_b |#{q: argmax_c != C - 1} - tgt_len[b]|
+ *                                class_error[0] = 100 - 100 #{matched rows of layer 0 whose argmax is their label} / #{matched rows},
+ *                                100 when nothing is matched.
+ *                              loss_ce = sum_{b,q,c} focal(x, y) / num_boxes with y = 1 exactly where c == labels[tgt_of] (a label C is the
+ *                              no-object class: no positive element).  The focal term is evaluated in its STABLE form: with z = x for
+ *                              y = 0 and z = -x for y = 1,
+ *                                  focal = a_t softplus(z) exp(-gamma softplus(-z)),   softplus(+-z) = max(+-z, 0) + log1p(exp(-|z|)),
+ *                              a_t = alpha for y = 1, 1 - alpha for y = 0, 1 for alpha < 0.  No 1 - sigmoid(x) is formed in fp32: the
+ *                              reference's formulation loses the small elements and their gradients beyond |x| ~ 8.
+ *                              loss_bbox = sum |box - tbox| / num_boxes and loss_giou = sum (1 - GIoU) / num_boxes over the matched
+ *                              rows, operation by operation as l1_loss and box_ops.generalized_box_iou_pairs, compiled without FMA
+ *                              contraction; no guards: a zero-area pair gives NaN as in torch.  The arg-max takes the lowest index on
+ *                              ties and a NaN as the largest value; for C == 1 the cardinality prediction is 0, as the reference's.
+ *                              SUMS: accumulated in fp64, rounded to fp32 once.  Thread t of the layer's workgroup takes queries t,
+ *                              t + 256, ... of image 0, then of image 1, ...; a butterfly over the wave; the four waves in wave order
+ *                              through LDS: the order is a function of the shape alone.  No atomics; every output is written once.
+ *                              T == 0 and images without targets are valid (box losses 0); labels / tboxes may then be NULL.
+ *   tf_set_criterion_bwd_f32   one launch, one work-item per (l, b, q).  G [L, 3]: the gradients of the three losses.  Recomputes from
+ *                              the forward's inputs (nothing else is saved) and writes grad_logits [L, B, Q, C] and grad_boxes
+ *                              [L, B, Q, 4] (zeros in unmatched rows), every element once; no atomics, no workspace.  Either output
+ *                              may be NULL and is then skipped.  min / max hand half of the gradient to each operand at a tie and
+ *                              clamp passes it at 0, as torch.
+ *   tf_match_cost_f32          one launch, one work-item per (r, t): cost [R, T] =
+ *                                  w_bbox |boxes[r] - tgt_bbox[t]|_1 + w_class (pos - neg) + w_giou (-GIoU),
+ *                                  pos = alpha (1 - p)^gamma (-log(p + 1e-8)),  neg = (1 - alpha) p^gamma (-log(1 - p + 1e-8)),
+ *                              p = sigmoid(logits[r, tgt_ids[t]]), with 1 - p formed as sigmoid(-x), never as a subtraction.  The GIoU
+ *                              is the device function of the criterion.  R == 0 or T == 0: nothing to do.
+ * boxes / tboxes / tgt_bbox / grad_boxes 16-byte aligned, labels / tgt_ids 8-byte, everything else 4-byte; L B Q max(C, 4) < 2^31,
+ * R max(C, 4, T) < 2^31; num_boxes > 0.  Each result is a pure function of the arguments: bit-identical from call to call, on any stream
+ * and in a captured HIP graph.  Non-finite logits: a NaN logit makes its layer's loss_ce and its own gradient NaN and leaves every other
+ * layer and element as it was.
+ * Checked in this order, before any GPU work: NULL required pointers -> TF_MSDA_ERR_NULL_POINTER, dimensions / alignment ->
+ * TF_MSDA_ERR_BAD_DIMS.  The labels live on the device: a label outside [0, C] is found on the host side of the binding
+ * (fused.set_criterion, fused.match_cost: TF_MSDA_ERR_BAD_DIMS), not by a device assert; the kernels never read outside a row for one.
+ */
+int tf_set_criterion_fwd_f32(const float *logits, const float *boxes, const int *tgt_of, const int64_t *labels, const float *tboxes,
+                             const int *tgt_len, float *losses, float *card, float *class_error, int L, int B, int Q, int C, int T,
+                             float alpha, float gamma, float num_boxes, void *stream);
+int tf_set_criterion_bwd_f32(const float *G, const float *logits, const float *boxes, const int *tgt_of, const int64_t *labels,
+                             const float *tboxes, float *grad_logits, float *grad_boxes, int L, int B, int Q, int C, int T, float alpha,
+                             float gamma, float num_boxes, void *stream);
+int tf_match_cost_f32(const float *logits, const float *boxes, const int64_t *tgt_ids, const float *tgt_bbox, float *cost, int64_t R, int C,
+                      int T, float w_class, float w_bbox, float w_giou, float alpha, float gamma, void *stream);
+
+/*
  * Convolution of a channels_last activation through the same kernel (an implicit GEMM over the output pixels; the weight
  * fragments streamed from L2, only the shifted input pixels pass LDS): ks = 3 (padding 1) or 1 (no padding), stride 1 or 2.
  *   x [nimg, hin, win, cin] NHWC fp32, below 3 GiB;  y [nimg, hout, wout, cout] NHWC, below 3 GiB;  cin % 64 == 0

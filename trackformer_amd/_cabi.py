@@ -69,6 +69,9 @@ EXPORTED_SYMBOLS = (
     "tf_add_layernorm_train_f32",
     "tf_add_layernorm_bwd_workspace_bytes",
     "tf_add_layernorm_bwd_f32",
+    "tf_set_criterion_fwd_f32",
+    "tf_set_criterion_bwd_f32",
+    "tf_match_cost_f32",
     "tf_linear_split_add_f32",
     "tf_ffn_fused_f32",
     "tf_linear_res_ln_f32",
@@ -78,7 +81,7 @@ EXPORTED_SYMBOLS = (
     "tf_nms_host_f32",
 )
 
-ABI_VERSION = 7   # 7: tf_add_layernorm_train / _bwd (6: tf_msda_fused_prologue / _backward_epilogue; 5: tf_linear_grad_stats / wgrad / dgrad; 4: tf_msda_backward_det_* and TF_MSDA_ERR_WORKSPACE; 3: the split-product entry points take w_lo / w_scale / terms)
+ABI_VERSION = 8   # 8: tf_set_criterion_fwd / _bwd, tf_match_cost (7: tf_add_layernorm_train / _bwd; 6: tf_msda_fused_prologue / _backward_epilogue; 5: tf_linear_grad_stats / wgrad / dgrad; 4: tf_msda_backward_det_* and TF_MSDA_ERR_WORKSPACE; 3: the split-product entry points take w_lo / w_scale / terms)
 
 _lib = None
 
@@ -217,6 +220,13 @@ def lib():
     L.tf_add_layernorm_bwd_workspace_bytes.argtypes = [i64, ci]
     L.tf_add_layernorm_bwd_f32.restype = ci
     L.tf_add_layernorm_bwd_f32.argtypes = [vp] * 9 + [i64, i64, ci, vp]
+    cf = ctypes.c_float
+    L.tf_set_criterion_fwd_f32.restype = ci
+    L.tf_set_criterion_fwd_f32.argtypes = [vp] * 9 + [ci] * 5 + [cf, cf, cf, vp]
+    L.tf_set_criterion_bwd_f32.restype = ci
+    L.tf_set_criterion_bwd_f32.argtypes = [vp] * 8 + [ci] * 5 + [cf, cf, cf, vp]
+    L.tf_match_cost_f32.restype = ci
+    L.tf_match_cost_f32.argtypes = [vp] * 5 + [i64, ci, ci] + [cf] * 5 + [vp]
     L.tf_conv_packed_f32.restype = ci
     L.tf_conv_packed_f32.argtypes = [vp, vp, vp, vp, vp, vp] + [ci] * 10 + [vp]
     L.tf_mha_core_f32.restype = ci

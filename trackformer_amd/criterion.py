@@ -6,12 +6,13 @@ Same surface as the reference's SetCriterion (models/detr.py:139-443) and its he
 import copy
 import os
 
+import numpy as np
 import torch
 import torch.distributed as dist
 import torch.nn.functional as F
 from torch import nn
 
-from . import box_ops
+from . import box_ops, fused
 from .nested import nested_tensor_from_tensor_list
 
 
@@ -60,6 +61,57 @@ def set_layers_at_once(on):
     global _LAYERS_AT_ONCE
     prev, _LAYERS_AT_ONCE = _LAYERS_AT_ONCE, bool(on)
     return prev
+
+
+# THE FUSED ROUTE (opt-in): wherever _layers_at_once would be taken and the stacked predictions are fp32 on the device, the class
+# (focal), cardinality and box losses of all layers are ONE launch forward and one backward (fused.set_criterion; include/tf_fused.h:
+# THE SET CRITERION AND THE MATCHING COST) instead of _layers_at_once's several dozen.  The focal term is evaluated in its stable
+# form there, so the small elements of the loss and their gradients are accurate where the fp32 `1 - sigmoid(x)` of
+# sigmoid_focal_loss has lost them; the sums agree to fp32 rounding.  NOT covered (today's path): the two-stage `enc_outputs` losses,
+# masks (final layer, torch), the non-focal cross-entropy, unequal match counts, anything not fp32 on the device.  OFF by default:
+# whether it is faster inside a training step is a measurement (tools/bench_criterion.py, profiles/criterion_fused_bench.json).
+_fused = None    # None: follow TF_CRITERION_FUSED (unset: off)
+_fused_counts = {"own": 0, "torch": 0}
+
+
+def fused_enabled():
+    if _fused is not None:
+        return _fused
+    return os.environ.get("TF_CRITERION_FUSED", "0") not in ("", "0")
+
+
+def set_fused(on):
+    """Switch the fused criterion route on or off (process-wide; None: follow TF_CRITERION_FUSED again); returns the previous
+    setting."""
+    global _fused
+    prev = fused_enabled()
+    _fused = None if on is None else bool(on)
+    return fused._switched(prev, fused_enabled())
+
+
+def fused_counts(reset=False):
+    """How many SetCriterion.forward calls with the switch on ran the library's own kernels ("own") and how many kept today's path
+    ("torch")."""
+    out = dict(_fused_counts)
+    if reset:
+        for k in _fused_counts:
+            _fused_counts[k] = 0
+    return out
+
+
+def build_tgt_of(all_indices, sizes, num_queries):
+    """The matcher's host-side index pairs of every layer -> (tgt_of int32 [L, B, Q], tgt_len int32 [B]) as numpy arrays: the GLOBAL
+    index (into the images' concatenated targets) of the target matched to prediction (l, b, q), or -1.  all_indices[l][b] = (query
+    indices, target indices); sizes[b] = the number of targets of image b."""
+    L, B = len(all_indices), len(sizes)
+    tgt_len = np.asarray(sizes, dtype=np.int32)
+    offsets = np.concatenate([[0], np.cumsum(tgt_len)[:-1]]).astype(np.int64)
+    tgt_of = np.full((L, B, num_queries), -1, dtype=np.int32)
+    for l, ind in enumerate(all_indices):
+        for b, (src, tgt) in enumerate(ind):
+            if len(src):
+                tgt_of[l, b, np.asarray(src, dtype=np.int64)] = np.asarray(tgt, dtype=np.int64) + offsets[b]
+    return tgt_of, tgt_len
 
 
 def counts_match(indices, aux_indices):
@@ -227,6 +279,44 @@ class SetCriterion(nn.Module):
                 losses['loss_giou' + suffix[l]] = loss_giou[l]
         return losses
 
+    def _layers_fused(self, layer_outputs, targets, all_indices, num_boxes):
+        """_layers_at_once through fused.set_criterion: the same keys, 0-d views of one [L, 3] tensor (+ card [L], class_error [1]), or
+        None when the kernels do not take the stacked tensors (the caller keeps today's path).  The host builds tgt_of / tgt_len with
+        numpy from the matcher's host-side indices and uploads both in ONE copy."""
+        L = len(layer_outputs)
+        logits = [o['pred_logits'] for o in layer_outputs]
+        boxes = [o['pred_boxes'] for o in layer_outputs]
+        if any(t.shape != logits[0].shape for t in logits) or any(t.shape != boxes[0].shape for t in boxes):
+            return None
+        if not (logits[0].is_cuda and logits[0].dtype == torch.float32 and boxes[0].dtype == torch.float32 and logits[0].dim() == 3):
+            return None
+        all_labels = torch.cat([t["labels"] for t in targets])
+        all_boxes = torch.cat([t["boxes"] for t in targets])
+        if all_labels.numel() and (all_labels.dtype != torch.int64 or all_boxes.dtype != torch.float32 or all_boxes.device != logits[0].device):
+            return None
+        logits, boxes = torch.stack(logits), torch.stack(boxes)          # [L, B, Q, C], [L, B, Q, 4]
+        if not fused.criterion_applies(logits, boxes):
+            return None
+        B, Q = logits.shape[1:3]
+        tgt_of, tgt_len = build_tgt_of(all_indices, [len(t["labels"]) for t in targets], Q)
+        both = torch.from_numpy(np.concatenate([tgt_of.reshape(-1), tgt_len])).to(logits.device, non_blocking=True)
+        out, card, class_error = fused.set_criterion(logits, boxes, both[:L * B * Q], all_labels, all_boxes, both[L * B * Q:],
+                                                     self.focal_alpha, self.focal_gamma, num_boxes)
+        losses = {}
+        suffix = [''] + ['_%d' % i for i in range(L - 1)]
+        if 'labels' in self.losses:                                      # (the keys in _layers_at_once's order)
+            for l in range(L):
+                losses['loss_ce' + suffix[l]] = out[l, 0]
+            losses['class_error'] = class_error[0]
+        if 'cardinality' in self.losses:
+            for l in range(L):
+                losses['cardinality_error' + suffix[l]] = card[l]
+        if 'boxes' in self.losses:
+            for l in range(L):
+                losses['loss_bbox' + suffix[l]] = out[l, 1]
+                losses['loss_giou' + suffix[l]] = out[l, 2]
+        return losses
+
     @staticmethod
     def _offsets(targets):
         off, out = 0, []
@@ -275,9 +365,15 @@ class SetCriterion(nn.Module):
         losses = None
         if (_LAYERS_AT_ONCE and self.focal_loss and aux_list and all(ix is not None for ix in aux_indices) and counts_match(indices, aux_indices)
                 and all(loss in ('labels', 'cardinality', 'boxes', 'masks') for loss in self.losses)):
-            losses = self._layers_at_once([outputs_without_aux] + aux_list, targets, [indices] + list(aux_indices), num_boxes)
+            if fused_enabled():
+                losses = self._layers_fused([outputs_without_aux] + aux_list, targets, [indices] + list(aux_indices), num_boxes)
+                _fused_counts["own" if losses is not None else "torch"] += 1
+            if losses is None:
+                losses = self._layers_at_once([outputs_without_aux] + aux_list, targets, [indices] + list(aux_indices), num_boxes)
             if losses is not None and 'masks' in self.losses:   # (the final layer only, as in the loop)
                 losses.update(self.get_loss('masks', outputs, targets, indices, num_boxes))
+        elif fused_enabled():
+            _fused_counts["torch"] += 1
         if losses is None:
             losses = {}
             for loss in self.losses:

@@ -140,6 +140,7 @@ bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 
 }  // namespace
 
 #include "layernorm_bwd.h"
+#include "criterion.h"
 
 namespace {
 

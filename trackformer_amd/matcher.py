@@ -5,12 +5,48 @@ Same module surface as the reference's models/matcher.py (HungarianMatcher :12-1
 L1 + GIoU); the track-query constraints, which the reference writes with a Python double loop over
 every query (:104-125), are applied as three vectorised index assignments on the host copy.
 """
+import os
+
 import numpy as np
 import torch
 from scipy.optimize import linear_sum_assignment
 from torch import nn
 
+from . import fused
 from .box_ops import box_cxcywh_to_xyxy, generalized_box_iou
+
+# THE FUSED COST (opt-in): with focal_loss set and fp32 tensors on the device, match_many builds the cost matrix of all prediction
+# sets with ONE kernel (fused.match_cost; include/tf_fused.h: tf_match_cost_f32) instead of the ~25 launches of the torch chain below;
+# 1 - p is formed as sigmoid(-x) there, never as an fp32 subtraction.  NOT covered: the softmax (plain DETR) cost; the track-query
+# constraints and linear_sum_assignment work on the host copy as before, and the cost still reaches the host in ONE copy.  OFF by
+# default (tools/bench_criterion.py, profiles/criterion_fused_bench.json).
+_fused_cost = None    # None: follow TF_MATCHER_FUSED_COST (unset: off)
+_fused_cost_counts = {"own": 0, "torch": 0}
+
+
+def fused_cost_enabled():
+    if _fused_cost is not None:
+        return _fused_cost
+    return os.environ.get("TF_MATCHER_FUSED_COST", "0") not in ("", "0")
+
+
+def set_fused_cost(on):
+    """Switch the fused matching cost on or off (process-wide; None: follow TF_MATCHER_FUSED_COST again); returns the previous
+    setting."""
+    global _fused_cost
+    prev = fused_cost_enabled()
+    _fused_cost = None if on is None else bool(on)
+    return fused._switched(prev, fused_cost_enabled())
+
+
+def fused_cost_counts(reset=False):
+    """How many match_many calls with the switch on built their cost with the library's own kernel ("own") and how many kept the torch
+    chain ("torch")."""
+    out = dict(_fused_cost_counts)
+    if reset:
+        for k in _fused_cost_counts:
+            _fused_cost_counts[k] = 0
+    return out
 
 
 class HungarianMatcher(nn.Module):
@@ -41,11 +77,23 @@ class HungarianMatcher(nn.Module):
         n_sets = len(outputs_list)
         batch_size, num_queries = outputs_list[0]["pred_logits"].shape[:2]
         logits = torch.stack([o["pred_logits"] for o in outputs_list]).flatten(0, 2)       # [sets * B * Q, C]
-        out_prob = logits.sigmoid() if self.focal_loss else logits.softmax(-1)
         out_bbox = torch.stack([o["pred_boxes"] for o in outputs_list]).flatten(0, 2)
         tgt_ids = torch.cat([v["labels"] for v in targets])
         tgt_bbox = torch.cat([v["boxes"] for v in targets])
+        cost_matrix = None
+        if fused_cost_enabled():
+            if self.focal_loss:
+                cost_matrix = fused.match_cost(logits, out_bbox, tgt_ids, tgt_bbox, self.cost_class, self.cost_bbox, self.cost_giou,
+                                               self.focal_alpha, self.focal_gamma)
+            _fused_cost_counts["own" if cost_matrix is not None else "torch"] += 1
+        if cost_matrix is None:
+            cost_matrix = self._cost_torch(logits, out_bbox, tgt_ids, tgt_bbox)
+        cost_all = cost_matrix.view(n_sets, batch_size, num_queries, -1).cpu()
+        return self._assign(cost_all, targets, n_sets, num_queries)
 
+    def _cost_torch(self, logits, out_bbox, tgt_ids, tgt_bbox):
+        """The cost matrix [sets * B * Q, T] by the reference's chain of device kernels."""
+        out_prob = logits.sigmoid() if self.focal_loss else logits.softmax(-1)
         if self.focal_loss:
             neg = (1 - self.focal_alpha) * (out_prob ** self.focal_gamma) \
                 * (-(1 - out_prob + 1e-8).log())
@@ -57,10 +105,12 @@ class HungarianMatcher(nn.Module):
         cost_bbox = torch.cdist(out_bbox, tgt_bbox, p=1)
         cost_giou = -generalized_box_iou(box_cxcywh_to_xyxy(out_bbox),
                                          box_cxcywh_to_xyxy(tgt_bbox))
-        cost_matrix = self.cost_bbox * cost_bbox + self.cost_class * cost_class \
+        return self.cost_bbox * cost_bbox + self.cost_class * cost_class \
             + self.cost_giou * cost_giou
-        cost_all = cost_matrix.view(n_sets, batch_size, num_queries, -1).cpu()
 
+    @staticmethod
+    def _assign(cost_all, targets, n_sets, num_queries):
+        """cost_all [sets, B, Q, T] on the host -> the index pairs of every set, track-query constraints applied."""
         sizes = [len(v["boxes"]) for v in targets]
         offsets = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64)
         constraints = []   # per sample: (false-positive mask, pinned rows, pinned columns) on the host, once for all sets
