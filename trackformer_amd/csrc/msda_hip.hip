@@ -53,6 +53,7 @@
 
 #include "tf_msda.h"
 #include "msda_common.h"
+#include "msda_dispatch.h"
 #include "msda_quad_geom.h"
 
 namespace {
@@ -1614,8 +1615,8 @@ bool is_aligned(const void *p, size_t a) { return (reinterpret_cast<uintptr_t>(p
 // Block -> pair mapping of the buffer-load forward kernel (TF_MSDA_HEAD_MAJOR=0/1, default 1).
 bool head_major_enabled()
 {
-    static const int on = [] { const char *e = getenv("TF_MSDA_HEAD_MAJOR"); return (e && e[0] == '0') ? 0 : 1; }();
-    return on != 0;
+    static const bool on = env_flag("TF_MSDA_HEAD_MAJOR", true);
+    return on;
 }
 unsigned head_major_grid(int N, int Lq, int M, int ppb)
 {
@@ -1652,56 +1653,22 @@ int tiled_mode()
 {
     const int g = g_tiled_mode.load(std::memory_order_relaxed);
     if (g >= 0) return g;
-    static const int env_mode = [] {
-        const char *e = getenv("TF_MSDA_TILED");   // unset: the LDS-window kernels; 0: off
-        if (!e || !e[0]) return 2;
-        return e[0] == '0' ? 0 : 2;
-    }();
+    static const int env_mode = env_flag("TF_MSDA_TILED", true) ? 2 : 0;   // unset: the LDS-window kernels; 0: off
     return env_mode;
-}
-
-// Largest number of queries any TH x TW tile holds (exact, same integer partition as the kernel).
-long long tile_max_queries(const LevelTable &lt, int L, int th, int tw)
-{
-    const int H0 = lt.H[0], W0 = lt.W[0];
-    long long max_nq = 0;   // exact, same integer partition as the kernel
-    for (int y0 = 0; y0 < H0; y0 += th)
-        for (int x0 = 0; x0 < W0; x0 += tw) {
-            const int y1 = (y0 + th < H0) ? y0 + th : H0, x1 = (x0 + tw < W0) ? x0 + tw : W0;
-            long long nq = 0;
-            for (int l = 0; l < L; ++l) {
-                const long long Hl = lt.H[l], Wl = lt.W[l];
-                const long long ny = (2 * y1 * Hl + H0 - 1) / (2LL * H0) - (2 * y0 * Hl + H0 - 1) / (2LL * H0);
-                const long long nx = (2 * x1 * Wl + W0 - 1) / (2LL * W0) - (2 * x0 * Wl + W0 - 1) / (2LL * W0);
-                nq += ny * nx;
-            }
-            if (nq > max_nq) max_nq = nq;
-        }
-    return max_nq;
 }
 
 // Tile plan of msda_bwd_f32_sorted2: the tile with the most queries that still fits kWinMaxQueries.
 bool plan_sorted(const LevelTable &lt, int L, int D, int P, WinGeom *wg)
 {
-    static const int on = [] { const char *e = getenv("TF_MSDA_BWD_SORTED"); return (e && e[0] == '0') ? 0 : 1; }();
+    static const bool on = env_flag("TF_MSDA_BWD_SORTED", true);
     if (!on || D != 32 || P != 4 || L > kWinLevels) return false;
     for (int l = 0; l < L; ++l)
         if (lt.H[l] >= 32768 || lt.W[l] >= 32768 || (long long)lt.H[l] * lt.W[l] >= (1 << kSortQueryShift)) return false;
-    struct Memo {
-        bool valid = false, ok = false;
-        int L = 0;
-        LevelTable lt;
-        WinGeom wg;
-    };
-    static thread_local Memo memo;
-    if (memo.valid && memo.L == L && memcmp(&memo.lt, &lt, sizeof(lt)) == 0) {
-        *wg = memo.wg;
+    static thread_local PlanMemo<WinGeom, 1> memo;
+    if (memo.hit({L}, lt)) {
+        *wg = memo.plan;
         return memo.ok;
     }
-    memo.valid = true;
-    memo.ok = false;
-    memo.L = L;
-    memo.lt = lt;
     int hy = 8, hx = 14, th = 0, tw = 0;
     if (const char *e = getenv("TF_MSDA_BWD_HALO")) sscanf(e, "%d,%d", &hy, &hx);
     if (const char *e = getenv("TF_MSDA_BWD_TILE")) sscanf(e, "%d,%d", &th, &tw);
@@ -1729,12 +1696,9 @@ bool plan_sorted(const LevelTable &lt, int L, int D, int P, WinGeom *wg)
     wg->tiles_y = (lt.H[0] + bth - 1) / bth;
     wg->tiles_x = (lt.W[0] + btw - 1) / btw;
     wg->cap_rows = kSortRowsCap;
-    memo.wg = *wg;
-    memo.ok = true;
+    memo.keep(*wg);
     return true;
 }
-
-bool raise_dynamic_lds_limit(const void *fn);   // per (function, device), below
 
 // ---- msda_fwd_f32_quad: options, tile plan, launch ----------------------------------------------------
 // Performance knobs (process-wide; tf_msda_set_option / TF_MSDA_QUAD="ta=12,waves=8,npass=1,lds=53,...").
@@ -1743,32 +1707,8 @@ const char *const kQuadOptNames[kQoCount] = {"quad_ta_mask", "quad_waves", "quad
                                              "quad_halo_x",  "quad_tile_h", "quad_tile_w", "quad_split"};
 const char *const kQuadEnvKeys[kQoCount] = {"ta", "waves", "npass", "lds", "hy", "hx", "th", "tw", "split"};
 constexpr int kQuadOptDefaults[kQoCount] = {0, 4, 3, 40, 6, 10, 0, 0, 1};
-std::atomic<int> g_quad_opt[kQoCount];
-std::atomic<int> g_quad_epoch{0};   // bumped by every change: invalidates the per-thread tile plans
+OptionTable<kQoCount> g_quad_opt{"TF_MSDA_QUAD", kQuadOptNames, kQuadEnvKeys, kQuadOptDefaults};
 std::atomic<unsigned long long *> g_quad_trace{nullptr};   // tf_msda_debug_trace_buffer
-
-void quad_opts_init()
-{
-    static const bool once = [] {
-        for (int i = 0; i < kQoCount; ++i) g_quad_opt[i].store(kQuadOptDefaults[i]);
-        if (const char *e = getenv("TF_MSDA_QUAD")) {
-            // comma-separated key=value list
-            const char *p = e;
-            while (*p) {
-                const char *eq = strchr(p, '=');
-                if (!eq) break;
-                for (int i = 0; i < kQoCount; ++i)
-                    if ((size_t)(eq - p) == strlen(kQuadEnvKeys[i]) && strncmp(p, kQuadEnvKeys[i], eq - p) == 0)
-                        g_quad_opt[i].store(atoi(eq + 1));
-                const char *c = strchr(eq, ',');
-                if (!c) break;
-                p = c + 1;
-            }
-        }
-        return true;
-    }();
-    (void)once;
-}
 
 struct QuadPlan {
     QuadGeom geom;
@@ -1779,10 +1719,8 @@ struct QuadPlan {
 bool plan_quad(const LevelTable &lt, int L, int D, int P, QuadPlan *qp)
 {
     if (tiled_mode() != 2 || D != 32 || P != 4 || L > kQuadLevels) return false;
-    quad_opts_init();
     int o[kQoCount];
-    for (int i = 0; i < kQoCount; ++i) o[i] = g_quad_opt[i].load(std::memory_order_relaxed);
-    const int epoch = g_quad_epoch.load(std::memory_order_relaxed);
+    const int epoch = g_quad_opt.load(o);
     const int ta = o[kQoTaMask], waves = o[kQoWaves], npass = o[kQoNpass];
     const int split = o[kQoSplit];
     if ((ta != 0 && ta != 12) || (waves != 4 && waves != 8) || npass < 1 || npass > 3 ||
@@ -1795,22 +1733,11 @@ bool plan_quad(const LevelTable &lt, int L, int D, int P, QuadPlan *qp)
     const int cap_rows = (int)(((size_t)o[kQoLdsKb] * 1024 - kQuadHdrBytes) / 128 - 2) & ~7;
     if (cap_rows < 8) return false;
     const size_t need = (size_t)kQuadHdrBytes + (size_t)(2 + cap_rows) * 128;
-    struct Memo {
-        bool valid = false, ok = false;
-        int L = 0, epoch = -1;
-        LevelTable lt;
-        QuadPlan qp;
-    };
-    static thread_local Memo memo;
-    if (memo.valid && memo.L == L && memo.epoch == epoch && memcmp(&memo.lt, &lt, sizeof(lt)) == 0) {
-        *qp = memo.qp;
+    static thread_local PlanMemo<QuadPlan, 2> memo;
+    if (memo.hit({L, epoch}, lt)) {
+        *qp = memo.plan;
         return memo.ok;
     }
-    memo.valid = true;
-    memo.ok = false;
-    memo.L = L;
-    memo.epoch = epoch;
-    memo.lt = lt;
     // tile: the most queries per (estimated) window row among the tiles that fill the workgroup
     const long long cap_q = (long long)waves * 16 * npass;
     int bth = 0, btw = 0;
@@ -1853,11 +1780,9 @@ bool plan_quad(const LevelTable &lt, int L, int D, int P, QuadPlan *qp)
     r.waves = waves;
     r.npass = npass;
     r.split = split;
-    memo.qp = r;
-    memo.ok = true;
+    memo.keep(r);
     *qp = r;
-    static const bool verbose = getenv("TF_MSDA_VERBOSE") != nullptr;
-    if (verbose)
+    if (msda_verbose())
         fprintf(stderr, "[tf_msda] quad plan: tile %dx%d (%lld queries max of %lld), %dx%d tiles, ta_mask %d, %d waves x %d "
                         "passes, split %d, %d window rows, %zu B LDS\n", bth, btw, tile_max_queries(lt, L, bth, btw), cap_q,
                 r.geom.tiles_y, r.geom.tiles_x, ta, waves, npass, split, cap_rows, need);
@@ -1878,34 +1803,11 @@ const void *quad_kernel_ta(int ta, int waves, int npass)
     return ta == 0 ? quad_kernel_wn<FUSED, 0, ROUND0>(waves, npass) : quad_kernel_wn<FUSED, 12, ROUND0>(waves, npass);
 }
 template <bool FUSED>
-const void *quad_kernel(int ta, int waves, int npass, int split)
+KernelVariant quad_variant(const QuadPlan &qp)
 {
     // split: level 0's window alone in a first round, the other levels' windows reuse its LDS rows
-    return split ? quad_kernel_ta<FUSED, 0x1>(ta, waves, npass) : quad_kernel_ta<FUSED, 0xF>(ta, waves, npass);
-}
-
-// The dynamic-LDS limit (hipFuncAttributeMaxDynamicSharedMemorySize) is an attribute of a function ON A DEVICE:
-// raised once per (function, current device), remembered in a small lock-protected table.
-bool raise_dynamic_lds_limit(const void *fn)
-{
-    struct Entry { const void *fn; int dev; };
-    static Entry table[256];
-    static std::atomic<int> count{0};
-    static std::atomic_flag lock = ATOMIC_FLAG_INIT;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return false;
-    const int n = count.load(std::memory_order_acquire);
-    for (int i = 0; i < n; ++i)
-        if (table[i].fn == fn && table[i].dev == dev) return true;
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return false;
-    while (lock.test_and_set(std::memory_order_acquire)) {}
-    const int k = count.load(std::memory_order_relaxed);
-    if (k < 256) {
-        table[k] = Entry{fn, dev};
-        count.store(k + 1, std::memory_order_release);
-    }
-    lock.clear(std::memory_order_release);
-    return true;
+    return {qp.split ? quad_kernel_ta<FUSED, 0x1>(qp.ta_mask, qp.waves, qp.npass) : quad_kernel_ta<FUSED, 0xF>(qp.ta_mask, qp.waves, qp.npass),
+            FUSED ? "msda_fwd_f32_quad<fused>" : "msda_fwd_f32_quad<plain>"};
 }
 
 // Launch msda_fwd_f32_quad for encoder-shaped calls (Lq == S, host shapes).  Returns false if not taken.
@@ -1919,34 +1821,20 @@ bool launch_quad(bool fused, const DirectArgs &da, const LevelTable &lt, int N, 
     if (!plan_quad(lt, da.L, D, P, &qp)) return false;
     const long long grid = (long long)N * qp.geom.tiles_y * qp.geom.tiles_x * da.M;
     if (grid > 0x7fffffffLL) return false;
-    const void *fn = fused ? quad_kernel<true>(qp.ta_mask, qp.waves, qp.npass, qp.split)
-                           : quad_kernel<false>(qp.ta_mask, qp.waves, qp.npass, qp.split);
-    if (!raise_dynamic_lds_limit(fn)) return false;
+    const KernelVariant kv = fused ? quad_variant<true>(qp) : quad_variant<false>(qp);
+    if (!raise_dynamic_lds_limit(kv.fn)) return false;
     qp.geom.trace = g_quad_trace.load(std::memory_order_relaxed);
     void *argv[] = {(void *)&da, (void *)&lt, (void *)&qp.geom};
-    *err = hipLaunchKernel(fn, dim3((unsigned)grid), dim3(qp.waves * 64), argv, qp.lds, stream);
-    note_kernel(fused ? "msda_fwd_f32_quad<fused>" : "msda_fwd_f32_quad<plain>");
+    *err = hipLaunchKernel(kv.fn, dim3((unsigned)grid), dim3(qp.waves * 64), argv, qp.lds, stream);
+    note_kernel(kv.name);
     return true;
 }
 
 // Launch msda_fwd_f32_direct when the shape qualifies (D == 32, P == 4, L <= 8).  Returns false if not.
 bool direct_enabled()
 {
-    static const int on = [] { const char *e = getenv("TF_MSDA_DIRECT"); return (e && e[0] == '0') ? 0 : 1; }();
-    return on != 0;
-}
-
-// dynamic LDS above 64 KB needs the per-function, per-device attribute: set once per device for msda_bwd_f32_sorted2
-bool raise_dynamic_lds(const void *fn)
-{
-    static std::atomic<unsigned long long> done{0};   // bit d: device d has the attribute
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (done.load(std::memory_order_acquire) & bit) return true;
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return false;
-    done.fetch_or(bit, std::memory_order_release);
-    return true;
+    static const bool on = env_flag("TF_MSDA_DIRECT", true);
+    return on;
 }
 
 std::atomic<int> g_direct9{-1};   // -1: environment (TF_MSDA_DIRECT9, default 1 since round 3: cfg-4 decoder forward 18.8-19.7 -> 12.7-14.0 us,
@@ -1955,52 +1843,87 @@ bool direct9_enabled()
 {
     const int v = g_direct9.load(std::memory_order_relaxed);
     if (v >= 0) return v != 0;
-    static const int env = [] { const char *e = getenv("TF_MSDA_DIRECT9"); return (e && e[0] == '0') ? 0 : 1; }();
-    return env != 0;
+    static const bool env = env_flag("TF_MSDA_DIRECT9", true);
+    return env;
+}
+
+template <bool FUSED>
+KernelVariant direct_variant(bool d9, int lpairs)
+{
+    if (d9)
+        return {lpairs == 1   ? (const void *)&msda_fwd_f32_direct9<1, FUSED>
+                : lpairs == 2 ? (const void *)&msda_fwd_f32_direct9<2, FUSED>
+                : lpairs == 3 ? (const void *)&msda_fwd_f32_direct9<3, FUSED>
+                              : (const void *)&msda_fwd_f32_direct9<4, FUSED>,
+                FUSED ? "msda_fwd_f32_direct9<fused>" : "msda_fwd_f32_direct9<plain>"};
+    return {lpairs == 1   ? (const void *)&msda_fwd_f32_direct<1, FUSED>
+            : lpairs == 2 ? (const void *)&msda_fwd_f32_direct<2, FUSED>
+            : lpairs == 3 ? (const void *)&msda_fwd_f32_direct<3, FUSED>
+                          : (const void *)&msda_fwd_f32_direct<4, FUSED>,
+            FUSED ? "msda_fwd_f32_direct<fused>" : "msda_fwd_f32_direct<plain>"};
 }
 
 bool launch_direct(bool fused, const DirectArgs &da, const LevelTable &lt, const int64_t *shapes_dev,
                    int D, int P, hipStream_t stream, hipError_t *err)
 {
     if (!direct_enabled() || P != 4 || da.L > 8) return false;
+    const bool d9 = D == 36;   // 9 lanes per pair, 28 pairs per workgroup (D == 32: 8 lanes, 32 pairs)
+    if (d9 ? !direct9_enabled() : D != 32) return false;
     const int lpairs = (da.L + 1) / 2;
-    const void *fn = nullptr;
-    if (D == 36) {   // 9 lanes per pair, 28 pairs per workgroup
-        if (!direct9_enabled()) return false;
-        if (fused)
-            fn = lpairs == 1   ? (const void *)&msda_fwd_f32_direct9<1, true>
-                 : lpairs == 2 ? (const void *)&msda_fwd_f32_direct9<2, true>
-                 : lpairs == 3 ? (const void *)&msda_fwd_f32_direct9<3, true>
-                               : (const void *)&msda_fwd_f32_direct9<4, true>;
-        else
-            fn = lpairs == 1   ? (const void *)&msda_fwd_f32_direct9<1, false>
-                 : lpairs == 2 ? (const void *)&msda_fwd_f32_direct9<2, false>
-                 : lpairs == 3 ? (const void *)&msda_fwd_f32_direct9<3, false>
-                               : (const void *)&msda_fwd_f32_direct9<4, false>;
-        const long long ppb = (kThreads / 64) * 7;
-        const long long grid9 = (da.nlq + ppb - 1) / ppb * da.M;
-        if (grid9 > 0x7fffffffLL) return false;
-        *err = launch(fn, (unsigned)grid9, 0, stream, da, lt, shapes_dev);
-        note_kernel(fused ? "msda_fwd_f32_direct9<fused>" : "msda_fwd_f32_direct9<plain>");
-        return true;
-    }
-    if (D != 32) return false;
-    if (fused)
-        fn = lpairs == 1   ? (const void *)&msda_fwd_f32_direct<1, true>
-             : lpairs == 2 ? (const void *)&msda_fwd_f32_direct<2, true>
-             : lpairs == 3 ? (const void *)&msda_fwd_f32_direct<3, true>
-                           : (const void *)&msda_fwd_f32_direct<4, true>;
-    else
-        fn = lpairs == 1   ? (const void *)&msda_fwd_f32_direct<1, false>
-             : lpairs == 2 ? (const void *)&msda_fwd_f32_direct<2, false>
-             : lpairs == 3 ? (const void *)&msda_fwd_f32_direct<3, false>
-                           : (const void *)&msda_fwd_f32_direct<4, false>;
-    const long long chunks = (da.nlq + (kThreads / 8) - 1) / (kThreads / 8);
-    const long long grid = chunks * da.M;
+    const KernelVariant kv = fused ? direct_variant<true>(d9, lpairs) : direct_variant<false>(d9, lpairs);
+    const long long ppb = d9 ? (kThreads / 64) * 7 : kThreads / 8;
+    const long long grid = (da.nlq + ppb - 1) / ppb * da.M;
     if (grid > 0x7fffffffLL) return false;
-    *err = launch(fn, (unsigned)grid, 0, stream, da, lt, shapes_dev);
-    note_kernel(fused ? "msda_fwd_f32_direct<fused>" : "msda_fwd_f32_direct<plain>");
+    *err = launch(kv.fn, (unsigned)grid, 0, stream, da, lt, shapes_dev);
+    note_kernel(kv.name);
     return true;
+}
+
+template <bool FUSED>
+KernelVariant fwd_buf_variant(int P)
+{
+    return {P == 1   ? (const void *)&msda_fwd_f32_buf<1, FUSED>
+            : P == 2 ? (const void *)&msda_fwd_f32_buf<2, FUSED>
+            : P == 4 ? (const void *)&msda_fwd_f32_buf<4, FUSED>
+                     : (const void *)&msda_fwd_f32_buf<8, FUSED>,
+            FUSED ? "msda_fwd_f32_buf<fused>" : "msda_fwd_f32_buf<plain>"};
+}
+
+// The fp32 fast path of both forward entries for an already-filled DirectArgs: the LDS-window kernels (persistent,
+// then one workgroup per tile), the row-gather kernel, then msda_fwd_f32_buf, which takes every call that got here.
+int forward_f32_chain(bool fused, const DirectArgs &da, const LevelTable &lt, const int64_t *shapes_dev, int N, int D,
+                      int P, const Plan &pl, hipStream_t stream)
+{
+    hipError_t e;
+    // plain entry: the first three read loc as 8-byte pairs, and the LDS-window kernels need the shapes on the host
+    const bool pairs = fused || is_aligned(da.loc, 8), host = shapes_dev == nullptr;
+    if (pairs && ((host && tiled_mode() == 2 && launch_pquad(fused, da, lt, N, D, P, stream, &e)) ||
+                  (host && launch_quad(fused, da, lt, N, D, P, stream, &e)) ||
+                  launch_direct(fused, da, lt, shapes_dev, D, P, stream, &e)))
+        return record_hip(e);
+    const KernelVariant kv = fused ? fwd_buf_variant<true>(P) : fwd_buf_variant<false>(P);
+    FusedArgs fa = da.fa;
+    fa.head_major = head_major_enabled() ? 1 : 0;
+    const unsigned grid = fa.head_major ? head_major_grid(N, da.Lq, da.M, pl.ppb) : pl.grid;
+    const long long total_pairs = (long long)N * da.Lq * da.M;
+    e = launch(kv.fn, grid, pl.lds, stream, da.value, da.value_bytes, da.loc, da.attn, da.out, lt, shapes_dev, da.S, da.M,
+               D, da.L, da.Lq, total_pairs, pl.ppb, pl.DV, fa);
+    note_kernel(kv.name);
+    return record_hip(e);
+}
+
+DirectArgs direct_args(const float *value, float *out, int N, int S, int M, int D, int L, int Lq)
+{
+    DirectArgs da{};
+    da.value = value;
+    da.value_bytes = (unsigned)((long long)N * S * M * D * 4);
+    da.out = out;
+    da.S = S;
+    da.M = M;
+    da.L = L;
+    da.Lq = Lq;
+    da.nlq = (long long)N * Lq;
+    return da;
 }
 
 template <typename T>
@@ -2024,49 +1947,20 @@ int forward_impl(const T *value, const int64_t *shapes_host, const int64_t *shap
     const int rc = make_plan<T>(N, M, D, L, Lq, P, 3, aligned, &pl);
     if (rc != TF_MSDA_OK) return rc;
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
-    const long long total_pairs = (long long)N * Lq * M;
-    hipError_t e;
     if constexpr (sizeof(T) == 4) {
         if (pl.vec == 4 && (P == 1 || P == 2 || P == 4 || P == 8) &&
             buf_path_ok(lt, shapes_host != nullptr, N, S, M, D, L)) {
-            const unsigned vbytes = (unsigned)((long long)N * S * M * D * 4);
-            {
-                DirectArgs da{};
-                da.value = value;
-                da.value_bytes = vbytes;
-                da.loc = loc;
-                da.attn = attn;
-                da.out = out;
-                da.S = S;
-                da.M = M;
-                da.L = L;
-                da.Lq = Lq;
-                da.nlq = (long long)N * Lq;
-                if (is_aligned(loc, 8) && shapes_dev == nullptr && tiled_mode() == 2 &&
-                    launch_pquad(false, da, lt, N, D, P, stream, &e))
-                    return record_hip(e);
-                if (is_aligned(loc, 8) && shapes_dev == nullptr && launch_quad(false, da, lt, N, D, P, stream, &e))
-                    return record_hip(e);
-                if (is_aligned(loc, 8) && launch_direct(false, da, lt, shapes_dev, D, P, stream, &e))
-                    return record_hip(e);
-            }
-            const void *fn = P == 1   ? (const void *)&msda_fwd_f32_buf<1, false>
-                             : P == 2 ? (const void *)&msda_fwd_f32_buf<2, false>
-                             : P == 4 ? (const void *)&msda_fwd_f32_buf<4, false>
-                                      : (const void *)&msda_fwd_f32_buf<8, false>;
-            FusedArgs none{};
-            none.head_major = head_major_enabled() ? 1 : 0;
-            const unsigned grid = none.head_major ? head_major_grid(N, Lq, M, pl.ppb) : pl.grid;
-            e = launch(fn, grid, pl.lds, stream, value, vbytes, loc, attn, out, lt, shapes_dev,
-                       S, M, D, L, Lq, total_pairs, pl.ppb, pl.DV, none);
-            note_kernel("msda_fwd_f32_buf<plain>");
-            return record_hip(e);
+            DirectArgs da = direct_args(value, out, N, S, M, D, L, Lq);
+            da.loc = loc;
+            da.attn = attn;
+            return forward_f32_chain(false, da, lt, shapes_dev, N, D, P, pl, stream);
         }
     }
     const void *fn = pl.vec == 4 ? (const void *)&msda_fwd_rowgather<T, 4>
                                  : (const void *)&msda_fwd_rowgather<T, 1>;
-    e = launch(fn, pl.grid, pl.lds, stream, value, loc, attn, out, lt, shapes_dev, S, M, D, L, Lq,
-               P, total_pairs, pl.ppb, pl.DV);
+    const long long total_pairs = (long long)N * Lq * M;
+    const hipError_t e = launch(fn, pl.grid, pl.lds, stream, value, loc, attn, out, lt, shapes_dev, S, M, D, L, Lq,
+                                P, total_pairs, pl.ppb, pl.DV);
     note_kernel(sizeof(T) == 4 ? "msda_fwd_rowgather<f32>" : "msda_fwd_rowgather<f64>");
     return record_hip(e);
 }
@@ -2093,41 +1987,19 @@ int forward_fused_impl(const float *value, const int64_t *shapes_host, const flo
     Plan pl;
     rc = make_plan<float>(N, M, D, L, Lq, P, 3, true, &pl);
     if (rc != TF_MSDA_OK) return rc;
-    const unsigned vbytes = (unsigned)((long long)N * S * M * D * 4);
-    const long long total_pairs = (long long)N * Lq * M;
-    {
-        DirectArgs da{};
-        da.value = value;
-        da.value_bytes = vbytes;
-        da.out = out;
-        da.fa = FusedArgs{ref, qproj, ref_dim, ld, off_col, logit_col, 1};
-        da.S = S;
-        da.M = M;
-        da.L = L;
-        da.Lq = Lq;
-        da.nlq = (long long)N * Lq;
-        hipError_t de;
-        if (tiled_mode() == 2 && launch_pquad(true, da, lt, N, D, P, static_cast<hipStream_t>(stream_v), &de))
-            return record_hip(de);
-        if (launch_quad(true, da, lt, N, D, P, static_cast<hipStream_t>(stream_v), &de))
-            return record_hip(de);
-        if (launch_direct(true, da, lt, nullptr, D, P, static_cast<hipStream_t>(stream_v), &de))
-            return record_hip(de);
-    }
-    const void *fn = P == 1   ? (const void *)&msda_fwd_f32_buf<1, true>
-                     : P == 2 ? (const void *)&msda_fwd_f32_buf<2, true>
-                     : P == 4 ? (const void *)&msda_fwd_f32_buf<4, true>
-                              : (const void *)&msda_fwd_f32_buf<8, true>;
-    const int hm = head_major_enabled() ? 1 : 0;
-    const FusedArgs fa{ref, qproj, ref_dim, ld, off_col, logit_col, hm};
-    const float *nul = nullptr;
-    const int64_t *nod = nullptr;
-    const unsigned grid = hm ? head_major_grid(N, Lq, M, pl.ppb) : pl.grid;
-    const hipError_t e = launch(fn, grid, pl.lds, static_cast<hipStream_t>(stream_v), value,
-                                vbytes, nul, nul, out, lt, nod, S, M, D, L, Lq, total_pairs, pl.ppb,
-                                pl.DV, fa);
-    note_kernel("msda_fwd_f32_buf<fused>");
-    return record_hip(e);
+    DirectArgs da = direct_args(value, out, N, S, M, D, L, Lq);
+    da.fa = FusedArgs{ref, qproj, ref_dim, ld, off_col, logit_col, 1};
+    return forward_f32_chain(true, da, lt, nullptr, N, D, P, pl, static_cast<hipStream_t>(stream_v));
+}
+
+template <bool ROWATOM>
+KernelVariant bwd_buf_variant(int P)
+{
+    return {P == 1   ? (const void *)&msda_bwd_f32_buf<1, ROWATOM>
+            : P == 2 ? (const void *)&msda_bwd_f32_buf<2, ROWATOM>
+            : P == 4 ? (const void *)&msda_bwd_f32_buf<4, ROWATOM>
+                     : (const void *)&msda_bwd_f32_buf<8, ROWATOM>,
+            ROWATOM ? "msda_bwd_f32_buf<rowatom>" : "msda_bwd_f32_buf"};
 }
 
 template <typename W>
@@ -2188,29 +2060,21 @@ int backward_impl(const T *value, const int64_t *shapes_host, const int64_t *sha
                 BwdSortArgs ba{value, vbytes, loc, attn, grad_out, grad_value, grad_loc, grad_attn, S, M, L};
                 const void *sfn = (const void *)&msda_bwd_f32_sorted2;
                 const size_t slds = (size_t)kSort2LdsBytes;
-                if (slds > 64 * 1024 && !raise_dynamic_lds(sfn)) return record_hip(hipErrorInvalidValue);
+                if (slds > 64 * 1024 && !raise_dynamic_lds_limit(sfn)) return record_hip(hipErrorInvalidValue);
                 void *argv[] = {(void *)&ba, (void *)&lt, (void *)&sgeom};
                 const unsigned sgrid = (unsigned)((long long)N * sgeom.tiles_y * sgeom.tiles_x * M);
                 note_kernel("msda_bwd_f32_sorted2");
                 return record_hip(hipLaunchKernel(sfn, dim3(sgrid), dim3(kWinThreads), argv, slds, stream));
             }
-            static const int rowatom_on = [] { const char *e = getenv("TF_MSDA_BWD_ROWATOM"); return (e && e[0] == '0') ? 0 : 1; }();
+            static const bool rowatom_on = env_flag("TF_MSDA_BWD_ROWATOM", true);
             const bool rowatom = rowatom_on && D == 32 && pl.DV == 8 && pl.ppb == kThreads / 8;
-            const void *bfn =
-                rowatom ? (P == 1   ? (const void *)&msda_bwd_f32_buf<1, true>
-                           : P == 2 ? (const void *)&msda_bwd_f32_buf<2, true>
-                           : P == 4 ? (const void *)&msda_bwd_f32_buf<4, true>
-                                    : (const void *)&msda_bwd_f32_buf<8, true>)
-                        : (P == 1   ? (const void *)&msda_bwd_f32_buf<1, false>
-                           : P == 2 ? (const void *)&msda_bwd_f32_buf<2, false>
-                           : P == 4 ? (const void *)&msda_bwd_f32_buf<4, false>
-                                    : (const void *)&msda_bwd_f32_buf<8, false>);
+            const KernelVariant kv = rowatom ? bwd_buf_variant<true>(P) : bwd_buf_variant<false>(P);
             if (rowatom) pl.lds = ((pl.lds + 15) & ~(size_t)15) + (size_t)pl.ppb * L * P * 32;
-            const hipError_t be = launch(bfn, head_major_grid(N, Lq, M, pl.ppb), pl.lds, stream,
+            const hipError_t be = launch(kv.fn, head_major_grid(N, Lq, M, pl.ppb), pl.lds, stream,
                                          value, vbytes, loc, attn, grad_out, grad_value, grad_loc,
                                          grad_attn, lt, shapes_dev, S, M, D, L, Lq, total_pairs,
                                          pl.ppb, pl.DV);
-            note_kernel(rowatom ? "msda_bwd_f32_buf<rowatom>" : "msda_bwd_f32_buf");
+            note_kernel(kv.name);
             return record_hip(be);
         }
     }
@@ -2277,13 +2141,7 @@ int tf_msda_set_option(const char *name, int value)
 {
     if (!name) return INT_MIN;
     if (strcmp(name, "tiled") == 0) return tf_msda_set_tiled(value);
-    quad_opts_init();
-    for (int i = 0; i < kQoCount; ++i)
-        if (strcmp(name, kQuadOptNames[i]) == 0) {
-            const int prev = g_quad_opt[i].exchange(value);
-            g_quad_epoch.fetch_add(1);
-            return prev;
-        }
+    if (strncmp(name, "quad_", 5) == 0) return g_quad_opt.set(name, value);
     if (strcmp(name, "direct9") == 0) return g_direct9.exchange(value < 0 ? -1 : (value ? 1 : 0));
     if (strcmp(name, "ffn_ti") == 0) return ffn_set_ti(value);
     if (strcmp(name, "ffn_tail_split") == 0) return ffn_set_tail_split(value);

@@ -48,6 +48,7 @@
 
 #include "tf_msda.h"
 #include "msda_common.h"
+#include "msda_dispatch.h"
 #include "msda_quad_geom.h"
 
 namespace {
@@ -109,7 +110,7 @@ struct PqRefs {     // fused entry only: reference points of the pair's query, p
     float rx[NPASS][kPqLevels], ry[NPASS][kPqLevels];
 };
 
-// PF: always 0.  (Register prefetch of the next tile's points, PF = 2: +23 VGPRs per pass -> two workgroups per CU, 50 vs
+// PF: removed, it was always 0.  (Register prefetch of the next tile's points, PF = 2: +23 VGPRs per pass -> two workgroups per CU, 50 vs
 //     43 us, removed in round 3.  An L2 prefetch by LDS-DMA into a sink: no effect, removed.  Round 3 also measured, and
 //     did not keep: window hints from the previous call with the level-0 DMA issued next to the point loads (two barriers
 //     fewer per tile, 47.0 vs 46.0 us), eight-wave workgroups (53 vs 47 us), four workgroups per CU at 128 VGPRs
@@ -118,7 +119,7 @@ struct PqRefs {     // fused entry only: reference points of the pair's query, p
 // WIDE: the points are loaded as 16-byte pieces (lane j of a quad reads level j's four points: 2 + 1 loads per pass
 //     instead of 4 + 4, every cache line fetched once) and transposed inside the quad by DPP so that lane j ends
 //     up with point j of every level.  Needs 16-byte aligned rows (the host checks).
-template <int NPASS, int PF>
+template <int NPASS>
 constexpr int pq_min_waves()
 {
     return NPASS == 1 ? 4 : NPASS == 2 ? 3 : 2;
@@ -150,12 +151,11 @@ __device__ __forceinline__ f32x4_t ldg_f4(const float *base, unsigned byte_off)
 
 // DH: head dimension, 32 (128-byte rows, 4 lanes x 8 channels) or 36 (hidden 288: 144-byte rows, 3 lanes x 12 channels,
 //     the window rows packed without padding and staged in 16-byte pieces; see msda_quad_dev.h).
-template <bool FUSED, int TA_MASK, int NPASS, int PF, bool WIDE, int DH>
-__global__ void __launch_bounds__(kPqThreads, (pq_min_waves<NPASS, PF>()))
+template <bool FUSED, int NPASS, bool WIDE, int DH>
+__global__ void __launch_bounds__(kPqThreads, (pq_min_waves<NPASS>()))
 msda_fwd_f32_pquad(const DirectArgs da, const LevelTable lt, const PquadGeom pg)
 {
     constexpr int PT = 4, D = DH, NL = kPqLevels, PAIRS = kPqPairs;
-    static_assert(PF == 0, "the register-prefetch variant (PF = 2) measured slower (50 vs 43 us, round 2) and was removed in round 3");
     constexpr bool D36 = DH == 36;
     constexpr unsigned ROWB = D * 4;   // bytes of one (pixel, head) row
     static_assert(DH == 32 || DH == 36, "head dimension 32 or 36");
@@ -409,63 +409,61 @@ msda_fwd_f32_pquad(const DirectArgs da, const LevelTable lt, const PquadGeom pg)
                 slot[2] = -1;
                 slot[3] = l < L ? Hs[l < NL ? l : 0] : INT_MIN;
             }
-        } else if constexpr (((TA_MASK >> l) & 1) == 0) {
-            if (l < L) {
-                int mnx = INT_MAX, mxx = INT_MIN, mny = INT_MAX, mxy = INT_MIN;
-                const float Wf = (float)Ws[l], Hf = (float)Hs[l];
+        } else if (l < L) {
+            int mnx = INT_MAX, mxx = INT_MIN, mny = INT_MAX, mxy = INT_MIN;
+            const float Wf = (float)Ws[l], Hf = (float)Hs[l];
 #pragma unroll
-                for (int ps = 0; ps < NPASS; ++ps) {
-                    const float xr = __builtin_fmaf(p.sx[ps][l], Wf, -0.5f);
-                    const float yr = __builtin_fmaf(p.sy[ps][l], Hf, -0.5f);
-                    const bool in = p.live[ps] && (yr > -1.f) && (xr > -1.f) && (yr < Hf) && (xr < Wf);
-                    const int x0 = (int)__builtin_floorf(in ? xr : 0.f), y0 = (int)__builtin_floorf(in ? yr : 0.f);
-                    mnx = min(mnx, in ? x0 : INT_MAX);
-                    mxx = max(mxx, in ? x0 : INT_MIN);
-                    mny = min(mny, in ? y0 : INT_MAX);
-                    mxy = max(mxy, in ? y0 : INT_MIN);
-                }
-                mnx = min(mnx, dpp_i<kDppQuadXor1>(mnx));
-                mxx = max(mxx, dpp_i<kDppQuadXor1>(mxx));
-                mny = min(mny, dpp_i<kDppQuadXor1>(mny));
-                mxy = max(mxy, dpp_i<kDppQuadXor1>(mxy));
-                mnx = min(mnx, dpp_i<kDppQuadXor2>(mnx));
-                mxx = max(mxx, dpp_i<kDppQuadXor2>(mxx));
-                mny = min(mny, dpp_i<kDppQuadXor2>(mny));
-                mxy = max(mxy, dpp_i<kDppQuadXor2>(mxy));
-                mnx = min(mnx, dpp_i<kDppRowRor4>(mnx));
-                mxx = max(mxx, dpp_i<kDppRowRor4>(mxx));
-                mny = min(mny, dpp_i<kDppRowRor4>(mny));
-                mxy = max(mxy, dpp_i<kDppRowRor4>(mxy));
-                mnx = min(mnx, dpp_i<kDppRowRor8>(mnx));
-                mxx = max(mxx, dpp_i<kDppRowRor8>(mxx));
-                mny = min(mny, dpp_i<kDppRowRor8>(mny));
-                mxy = max(mxy, dpp_i<kDppRowRor8>(mxy));
-                // the four DPP rows of the wave -> one box per wave (scalar), filed in the wave's own slot: LDS atomics
-                // (ds_min / ds_max on one address from every wave of the CU) serialise and cost microseconds per tile
-                const int a0 = __builtin_amdgcn_readlane(mnx, 0), a1 = __builtin_amdgcn_readlane(mnx, 16);
-                const int a2 = __builtin_amdgcn_readlane(mnx, 32), a3 = __builtin_amdgcn_readlane(mnx, 48);
-                const int b0 = __builtin_amdgcn_readlane(mxx, 0), b1 = __builtin_amdgcn_readlane(mxx, 16);
-                const int b2 = __builtin_amdgcn_readlane(mxx, 32), b3 = __builtin_amdgcn_readlane(mxx, 48);
-                const int c0 = __builtin_amdgcn_readlane(mny, 0), c1 = __builtin_amdgcn_readlane(mny, 16);
-                const int c2 = __builtin_amdgcn_readlane(mny, 32), c3 = __builtin_amdgcn_readlane(mny, 48);
-                const int d0 = __builtin_amdgcn_readlane(mxy, 0), d1 = __builtin_amdgcn_readlane(mxy, 16);
-                const int d2 = __builtin_amdgcn_readlane(mxy, 32), d3 = __builtin_amdgcn_readlane(mxy, 48);
-                const int wmnx = min(min(a0, a1), min(a2, a3)), wmxx = max(max(b0, b1), max(b2, b3));
-                const int wmny = min(min(c0, c1), min(c2, c3)), wmxy = max(max(d0, d1), max(d2, d3));
-                if (lane == 0) {
-                    int *slot = s_bb + ((par * 4 + wave) * 4 + l) * 4;
-                    slot[0] = wmnx;
-                    slot[1] = wmxx;
-                    slot[2] = wmny;
-                    slot[3] = wmxy;
-                }
-            } else if (l < NL && lane == 0) {   // levels the call does not have: an empty box
-                int *slot = s_bb + ((par * 4 + wave) * 4 + l) * 4;
-                slot[0] = INT_MAX;
-                slot[1] = INT_MIN;
-                slot[2] = INT_MAX;
-                slot[3] = INT_MIN;
+            for (int ps = 0; ps < NPASS; ++ps) {
+                const float xr = __builtin_fmaf(p.sx[ps][l], Wf, -0.5f);
+                const float yr = __builtin_fmaf(p.sy[ps][l], Hf, -0.5f);
+                const bool in = p.live[ps] && (yr > -1.f) && (xr > -1.f) && (yr < Hf) && (xr < Wf);
+                const int x0 = (int)__builtin_floorf(in ? xr : 0.f), y0 = (int)__builtin_floorf(in ? yr : 0.f);
+                mnx = min(mnx, in ? x0 : INT_MAX);
+                mxx = max(mxx, in ? x0 : INT_MIN);
+                mny = min(mny, in ? y0 : INT_MAX);
+                mxy = max(mxy, in ? y0 : INT_MIN);
             }
+            mnx = min(mnx, dpp_i<kDppQuadXor1>(mnx));
+            mxx = max(mxx, dpp_i<kDppQuadXor1>(mxx));
+            mny = min(mny, dpp_i<kDppQuadXor1>(mny));
+            mxy = max(mxy, dpp_i<kDppQuadXor1>(mxy));
+            mnx = min(mnx, dpp_i<kDppQuadXor2>(mnx));
+            mxx = max(mxx, dpp_i<kDppQuadXor2>(mxx));
+            mny = min(mny, dpp_i<kDppQuadXor2>(mny));
+            mxy = max(mxy, dpp_i<kDppQuadXor2>(mxy));
+            mnx = min(mnx, dpp_i<kDppRowRor4>(mnx));
+            mxx = max(mxx, dpp_i<kDppRowRor4>(mxx));
+            mny = min(mny, dpp_i<kDppRowRor4>(mny));
+            mxy = max(mxy, dpp_i<kDppRowRor4>(mxy));
+            mnx = min(mnx, dpp_i<kDppRowRor8>(mnx));
+            mxx = max(mxx, dpp_i<kDppRowRor8>(mxx));
+            mny = min(mny, dpp_i<kDppRowRor8>(mny));
+            mxy = max(mxy, dpp_i<kDppRowRor8>(mxy));
+            // the four DPP rows of the wave -> one box per wave (scalar), filed in the wave's own slot: LDS atomics
+            // (ds_min / ds_max on one address from every wave of the CU) serialise and cost microseconds per tile
+            const int a0 = __builtin_amdgcn_readlane(mnx, 0), a1 = __builtin_amdgcn_readlane(mnx, 16);
+            const int a2 = __builtin_amdgcn_readlane(mnx, 32), a3 = __builtin_amdgcn_readlane(mnx, 48);
+            const int b0 = __builtin_amdgcn_readlane(mxx, 0), b1 = __builtin_amdgcn_readlane(mxx, 16);
+            const int b2 = __builtin_amdgcn_readlane(mxx, 32), b3 = __builtin_amdgcn_readlane(mxx, 48);
+            const int c0 = __builtin_amdgcn_readlane(mny, 0), c1 = __builtin_amdgcn_readlane(mny, 16);
+            const int c2 = __builtin_amdgcn_readlane(mny, 32), c3 = __builtin_amdgcn_readlane(mny, 48);
+            const int d0 = __builtin_amdgcn_readlane(mxy, 0), d1 = __builtin_amdgcn_readlane(mxy, 16);
+            const int d2 = __builtin_amdgcn_readlane(mxy, 32), d3 = __builtin_amdgcn_readlane(mxy, 48);
+            const int wmnx = min(min(a0, a1), min(a2, a3)), wmxx = max(max(b0, b1), max(b2, b3));
+            const int wmny = min(min(c0, c1), min(c2, c3)), wmxy = max(max(d0, d1), max(d2, d3));
+            if (lane == 0) {
+                int *slot = s_bb + ((par * 4 + wave) * 4 + l) * 4;
+                slot[0] = wmnx;
+                slot[1] = wmxx;
+                slot[2] = wmny;
+                slot[3] = wmxy;
+            }
+        } else if (l < NL && lane == 0) {   // levels the call does not have: an empty box
+            int *slot = s_bb + ((par * 4 + wave) * 4 + l) * 4;
+            slot[0] = INT_MAX;
+            slot[1] = INT_MIN;
+            slot[2] = INT_MAX;
+            slot[3] = INT_MIN;
         }
     };
     auto bbox = [&](const PqPoints<NPASS> &p, int par) {
@@ -510,7 +508,7 @@ msda_fwd_f32_pquad(const DirectArgs da, const LevelTable lt, const PquadGeom pg)
             w.wy0 = kQuadFar;
             w.ww = w.wh = w.limx = w.limy = 0;
             bool fits = false;
-            if (l < L && ((TA_MASK >> l) & 1) == 0) {
+            if (l < L) {
                 const int *bb = s_bb + par * 64 + 4 * l;   // + 16 * wave
                 const int *nm4 = s_nom + par * 4 * kML;
                 int bx0 = INT_MAX, bx1 = INT_MIN, by0 = INT_MAX, by1 = INT_MIN;
@@ -543,7 +541,7 @@ msda_fwd_f32_pquad(const DirectArgs da, const LevelTable lt, const PquadGeom pg)
         const unsigned head_base = (unsigned)((((long long)cur.b * S * M + cur.m) * D) * 4);
         int gwx0[NL], gwy0[NL], glimx[NL], glimy[NL], gww[NL], groff[NL];
         unsigned glvl[NL];
-        bool by_loads[NL];   // the level is gathered by buffer loads (TA_MASK, or its window did not fit)
+        bool by_loads[NL];   // the level is gathered by buffer loads (its window did not fit)
 #pragma unroll
         for (int l = 0; l < NL; ++l) {
             glvl[l] = head_base + (unsigned)starts[l] * rowbytes;
@@ -559,7 +557,7 @@ msda_fwd_f32_pquad(const DirectArgs da, const LevelTable lt, const PquadGeom pg)
         auto phase_b = [&](auto lc, auto rc) {
             constexpr int l = decltype(lc)::value;
             constexpr int RMASK = decltype(rc)::value;
-            if constexpr (((TA_MASK >> l) & 1) == 0 && ((RMASK >> l) & 1) != 0) {
+            if constexpr (((RMASK >> l) & 1) != 0) {
                 if (l < L) {
                     const int H = Hs[l], W = Ws[l];
                     const int *ge = s_geo + (par * 4 + l) * 8;   // this level's window, computed by wave l after B0
@@ -649,10 +647,8 @@ msda_fwd_f32_pquad(const DirectArgs da, const LevelTable lt, const PquadGeom pg)
             constexpr int l = decltype(lc)::value;
             constexpr int ps = decltype(psc)::value < NPASS ? decltype(psc)::value : 0;   // (never called out of range)
             constexpr bool LDS_PHASE = decltype(ldsc)::value;
-            constexpr bool TA = ((TA_MASK >> l) & 1) != 0;
             if (l >= L) return;                          // uniform
-            if constexpr (TA && LDS_PHASE) return;
-            if (!TA && by_loads[l] == LDS_PHASE) return;   // uniform: a level runs in exactly one of the two phases
+            if (by_loads[l] == LDS_PHASE) return;        // uniform: a level runs in exactly one of the two phases
             if (ps * PAIRS >= cur.nq) return;            // uniform
             const int H = Hs[l], W = Ws[l];
             const float Wf = (float)W, Hf = (float)H;
@@ -722,12 +718,12 @@ msda_fwd_f32_pquad(const DirectArgs da, const LevelTable lt, const PquadGeom pg)
             if constexpr (NPASS > 1) levels(maskc, std::integral_constant<int, 1>{}, ldsc);
             if constexpr (NPASS > 2) levels(maskc, std::integral_constant<int, 2>{}, ldsc);
         };
-        constexpr int R0 = 0x1 & ~TA_MASK, R1 = 0xE & ~TA_MASK;   // LDS levels of the two rounds
+        constexpr int R0 = 0x1, R1 = 0xE;   // LDS levels of the two rounds
 
         // ---- round 0: level 0 ----
         used = 0;
         phase_b(std::integral_constant<int, 0>{}, std::integral_constant<int, R0>{});
-        all_passes(std::integral_constant<int, (0x1 | TA_MASK)>{}, std::false_type{});   // by buffer loads
+        all_passes(std::integral_constant<int, R0>{}, std::false_type{});   // by buffer loads
         __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): this wave's DMA landed
         __syncthreads();                      // B1: ... everybody's; the next tile's tables are visible
         if (iter == 0) stamp(4);
@@ -792,61 +788,18 @@ const char *const kPqEnvKeys[kPoCount] = {"wide", "npass", "lds", "hy", "hx", "t
 // v2: msda_fwd_f32_pquad2 (msda_pquad2.h) where it applies (D == 32, two passes, 16-byte aligned inputs)
 // waves: 4, or 8 (version 2 only: one pass of 128 pairs, two workgroups per CU -- use with lds=78)
 constexpr int kPqOptDefaults[kPoCount] = {1, 2, 52, 6, 10, 0, 0, 3, 0, 0, 1, 1, 4, 0, 0, 1, 0, 0, 0};   // 3 x 52 KB = 156 KB of the CU's 160
-std::atomic<int> g_pq_opt[kPoCount];
-std::atomic<int> g_pq_epoch{0};
+OptionTable<kPoCount> g_pq_opt{"TF_MSDA_PQUAD", kPqOptNames, kPqEnvKeys, kPqOptDefaults};
 std::atomic<unsigned long long *> g_pq_trace{nullptr};
 
-int pq_max_wgs(int npass, int pf)   // = pq_min_waves<NPASS, PF>(): workgroups per CU the register budget admits
+int pq_max_wgs(int npass)   // = pq_min_waves<NPASS>(): workgroups per CU the register budget admits
 {
-    (void)pf;
     return npass == 1 ? 4 : npass == 2 ? 3 : 2;
-}
-
-void pq_opts_init()
-{
-    static const bool once = [] {
-        for (int i = 0; i < kPoCount; ++i) g_pq_opt[i].store(kPqOptDefaults[i]);
-        if (const char *e = getenv("TF_MSDA_PQUAD")) {   // comma-separated key=value list, e.g. "on=0" or "npass=3,wgs=2"
-            const char *p = e;
-            while (*p) {
-                const char *eq = strchr(p, '=');
-                if (!eq) break;
-                for (int i = 0; i < kPoCount; ++i)
-                    if ((size_t)(eq - p) == strlen(kPqEnvKeys[i]) && strncmp(p, kPqEnvKeys[i], eq - p) == 0)
-                        g_pq_opt[i].store(atoi(eq + 1));
-                const char *c = strchr(eq, ',');
-                if (!c) break;
-                p = c + 1;
-            }
-        }
-        return true;
-    }();
-    (void)once;
-}
-
-long long pq_tile_max_queries(const LevelTable &lt, int L, int th, int tw)
-{
-    const int H0 = lt.H[0], W0 = lt.W[0];
-    long long max_nq = 0;   // exact, same integer partition as the kernel (tfq_tile_bound)
-    for (int y0 = 0; y0 < H0; y0 += th)
-        for (int x0 = 0; x0 < W0; x0 += tw) {
-            const int y1 = (y0 + th < H0) ? y0 + th : H0, x1 = (x0 + tw < W0) ? x0 + tw : W0;
-            long long nq = 0;
-            for (int l = 0; l < L; ++l) {
-                const long long Hl = lt.H[l], Wl = lt.W[l];
-                const long long ny = (2 * y1 * Hl + H0 - 1) / (2LL * H0) - (2 * y0 * Hl + H0 - 1) / (2LL * H0);
-                const long long nx = (2 * x1 * Wl + W0 - 1) / (2LL * W0) - (2 * x0 * Wl + W0 - 1) / (2LL * W0);
-                nq += ny * nx;
-            }
-            if (nq > max_nq) max_nq = nq;
-        }
-    return max_nq;
 }
 
 struct PqPlan {
     PquadGeom geom;
     size_t lds;
-    int ta_mask, npass, wgs, pf;
+    int npass, wgs;
     bool wide;
     bool v2;
     int waves;
@@ -868,16 +821,14 @@ int pq_num_cus()
 
 bool pq_plan(const LevelTable &lt, int L, int M, int N, int D, PqPlan *out)
 {
-    pq_opts_init();
     int o[kPoCount];
-    for (int i = 0; i < kPoCount; ++i) o[i] = g_pq_opt[i].load(std::memory_order_relaxed);
+    const int epoch = g_pq_opt.load(o);
     if (!o[kPoEnable]) return false;
-    const int epoch = g_pq_epoch.load(std::memory_order_relaxed);
-    const int ta = 0, npass = o[kPoNpass], pf = o[kPoPrefetch];
-    if (npass < 1 || npass > 3 || pf != 0 || o[kPoWgPerCu] < 1 || o[kPoSkew] < 0) return false;   // pquad_prefetch = 2: removed
+    const int npass = o[kPoNpass];
+    if (npass < 1 || npass > 3 || o[kPoPrefetch] != 0 || o[kPoWgPerCu] < 1 || o[kPoSkew] < 0) return false;   // pquad_prefetch = 2: removed
     // eight-wave workgroups (version 2 only, one pass of 128 pairs): two workgroups per CU (<= 128 registers)
     const int waves = (o[kPoV2] && D == 32 && o[kPoWaves] == 8 && npass == 1) ? 8 : 4;
-    const int max_wgs = waves == 8 ? 2 : pq_max_wgs(npass, pf);
+    const int max_wgs = waves == 8 ? 2 : pq_max_wgs(npass);
     const int wgs = o[kPoWgPerCu] < max_wgs ? o[kPoWgPerCu] : max_wgs;
     if (o[kPoLdsKb] < 8 || o[kPoLdsKb] > 160 || o[kPoHaloY] < 0 || o[kPoHaloX] < 0 || o[kPoTileH] < 0 || o[kPoTileW] < 0)
         return false;
@@ -888,31 +839,16 @@ bool pq_plan(const LevelTable &lt, int L, int M, int N, int D, PqPlan *out)
     int cap_rows = (int)(((size_t)o[kPoLdsKb] * 1024 - kPqHdrBytes - (D == 36 ? 1024 : 0)) / rowb - 2);
     if (D == 32) cap_rows &= ~7;
     if (cap_rows < 8) return false;
-    struct Memo {
-        bool valid = false, ok = false;
-        int L = 0, M = 0, N = 0, D = 0, epoch = -1;
-        LevelTable lt;
-        PqPlan plan;
-    };
-    static thread_local Memo memo;
-    if (memo.valid && memo.L == L && memo.M == M && memo.N == N && memo.D == D && memo.epoch == epoch &&
-        memcmp(&memo.lt, &lt, sizeof(lt)) == 0) {
+    static thread_local PlanMemo<PqPlan, 5> memo;
+    if (memo.hit({L, M, N, D, epoch}, lt)) {
         *out = memo.plan;
         return memo.ok;
     }
-    memo.valid = true;
-    memo.ok = false;
-    memo.L = L;
-    memo.M = M;
-    memo.N = N;
-    memo.D = D;
-    memo.epoch = epoch;
-    memo.lt = lt;
     const long long cap_q = (long long)(16 * waves) * npass;
     const long long slots = (long long)pq_num_cus() * wgs;
     int bth = 0, btw = 0;
     if (o[kPoTileH] > 0 && o[kPoTileW] > 0) {
-        const long long nq = pq_tile_max_queries(lt, L, o[kPoTileH], o[kPoTileW]);
+        const long long nq = tile_max_queries(lt, L, o[kPoTileH], o[kPoTileW]);
         if (nq >= 1 && nq <= cap_q) {
             bth = o[kPoTileH];
             btw = o[kPoTileW];
@@ -924,7 +860,7 @@ bool pq_plan(const LevelTable &lt, int L, int M, int N, int D, PqPlan *out)
         for (int th = 1; th <= 32; ++th)
             for (int tw = 2; tw <= 32; tw += 2) {
                 if ((long long)th * tw > cap_q) continue;
-                const long long nq = pq_tile_max_queries(lt, L, th, tw);
+                const long long nq = tile_max_queries(lt, L, th, tw);
                 if (nq < 1 || nq > cap_q) continue;
                 const long long items = (long long)N * ((lt.H[0] + th - 1) / th) * ((lt.W[0] + tw - 1) / tw) * M;
                 const long long rounds = (items + slots - 1) / slots;
@@ -963,40 +899,39 @@ bool pq_plan(const LevelTable &lt, int L, int M, int N, int D, PqPlan *out)
     r.wide = o[kPoWide] != 0;
     r.v2 = o[kPoV2] != 0;
     r.waves = waves;
-    r.ta_mask = ta;
     r.npass = npass;
     r.wgs = wgs;
-    r.pf = pf;
-    memo.plan = r;
-    memo.ok = true;
+    memo.keep(r);
     *out = r;
-    static const bool verbose = getenv("TF_MSDA_VERBOSE") != nullptr;
-    if (verbose)
+    if (msda_verbose())
         fprintf(stderr, "[tf_msda] pquad plan: tile %dx%d (%lld queries max of %lld), %dx%d tiles x %d heads = %lld items on "
-                        "%lld workgroups, ta_mask %d, %d passes, prefetch %d, %d window rows, %zu B LDS\n", bth, btw,
-                pq_tile_max_queries(lt, L, bth, btw), cap_q, r.geom.tiles_y, r.geom.tiles_x, M, items, slots, ta, npass, pf,
+                        "%lld workgroups, %d passes, %d window rows, %zu B LDS\n", bth, btw,
+                tile_max_queries(lt, L, bth, btw), cap_q, r.geom.tiles_y, r.geom.tiles_x, M, items, slots, npass,
                 cap_rows, r.lds);
     return true;
 }
 
-template <bool FUSED, bool WIDE>
-const void *pq_kernel_n(int npass)
+// The kernel of a plan: version 2 (msda_pquad2.h; `cf`: its conflict-free gather) or this file's.
+template <bool F>
+KernelVariant pquad_variant(const PqPlan &pl, int D, bool wide, bool v2, bool cf)
 {
-    return npass == 1   ? (const void *)&msda_fwd_f32_pquad<FUSED, 0, 1, 0, WIDE, 32>
-           : npass == 2 ? (const void *)&msda_fwd_f32_pquad<FUSED, 0, 2, 0, WIDE, 32>
-                        : (const void *)&msda_fwd_f32_pquad<FUSED, 0, 3, 0, WIDE, 32>;
-}
-// head dimension 36: 2 passes (the only variant built)
-template <bool FUSED>
-const void *pq_kernel_d36(bool wide)
-{
-    return wide ? (const void *)&msda_fwd_f32_pquad<FUSED, 0, 2, 0, true, 36>
-                : (const void *)&msda_fwd_f32_pquad<FUSED, 0, 2, 0, false, 36>;
-}
-template <bool FUSED>
-const void *pq_kernel(int npass, bool wide)
-{
-    return wide ? pq_kernel_n<FUSED, true>(npass) : pq_kernel_n<FUSED, false>(npass);
+    if (cf)
+        return pl.waves == 8 ? KernelVariant{(const void *)&msda_fwd_f32_pquad2<F, 8, 1, true>, F ? "msda_fwd_f32_pquad2<fused,8w,1p,cf>" : "msda_fwd_f32_pquad2<plain,8w,1p,cf>"}
+                             : KernelVariant{(const void *)&msda_fwd_f32_pquad2<F, 4, 2, true>, F ? "msda_fwd_f32_pquad2<fused,4w,2p,cf>" : "msda_fwd_f32_pquad2<plain,4w,2p,cf>"};
+    if (v2)
+        return pl.waves == 8   ? KernelVariant{(const void *)&msda_fwd_f32_pquad2<F, 8, 1>, F ? "msda_fwd_f32_pquad2<fused,8w,1p>" : "msda_fwd_f32_pquad2<plain,8w,1p>"}
+               : pl.npass == 1 ? KernelVariant{(const void *)&msda_fwd_f32_pquad2<F, 4, 1>, F ? "msda_fwd_f32_pquad2<fused,4w,1p>" : "msda_fwd_f32_pquad2<plain,4w,1p>"}
+                               : KernelVariant{(const void *)&msda_fwd_f32_pquad2<F, 4, 2>, F ? "msda_fwd_f32_pquad2<fused,4w,2p>" : "msda_fwd_f32_pquad2<plain,4w,2p>"};
+    if (D == 36)   // head dimension 36: 2 passes (the only variant built)
+        return {wide ? (const void *)&msda_fwd_f32_pquad<F, 2, true, 36> : (const void *)&msda_fwd_f32_pquad<F, 2, false, 36>,
+                F ? "msda_fwd_f32_pquad<fused,D=36>" : "msda_fwd_f32_pquad<plain,D=36>"};
+    const void *fn = wide ? (pl.npass == 1   ? (const void *)&msda_fwd_f32_pquad<F, 1, true, 32>
+                             : pl.npass == 2 ? (const void *)&msda_fwd_f32_pquad<F, 2, true, 32>
+                                             : (const void *)&msda_fwd_f32_pquad<F, 3, true, 32>)
+                          : (pl.npass == 1   ? (const void *)&msda_fwd_f32_pquad<F, 1, false, 32>
+                             : pl.npass == 2 ? (const void *)&msda_fwd_f32_pquad<F, 2, false, 32>
+                                             : (const void *)&msda_fwd_f32_pquad<F, 3, false, 32>);
+    return {fn, F ? "msda_fwd_f32_pquad<fused>" : "msda_fwd_f32_pquad<plain>"};
 }
 
 }  // namespace
@@ -1013,7 +948,7 @@ bool launch_pquad(bool fused, const DirectArgs &da, const LevelTable &lt, int N,
     if ((long long)N * da.Lq * da.M * da.L * 4 * 8 >= (1LL << 32)) return false;
     PqPlan pl;
     if (!pq_plan(lt, da.L, da.M, N, D, &pl)) return false;
-    if (D == 36 && (pl.npass != 2 || pl.pf != 0)) return false;
+    if (D == 36 && pl.npass != 2) return false;
     long long grid = (long long)pq_num_cus() * pl.wgs;
     if (grid > pl.geom.n_items) grid = pl.geom.n_items;
     // 16-byte loads of the points need 16-byte aligned rows
@@ -1023,61 +958,19 @@ bool launch_pquad(bool fused, const DirectArgs &da, const LevelTable &lt, int N,
                da.fa.logit_col % 4 == 0;
     else
         wide = wide && ((uintptr_t)da.loc % 16 == 0) && ((uintptr_t)da.attn % 16 == 0);
-    const bool v2 = pl.v2 && D == 32 && wide && pl.ta_mask == 0 && ((pl.waves == 4 && pl.npass <= 2) || (pl.waves == 8 && pl.npass == 1));
+    const bool v2 = pl.v2 && D == 32 && wide && ((pl.waves == 4 && pl.npass <= 2) || (pl.waves == 8 && pl.npass == 1));
     if (pl.waves == 8 && !v2) return false;   // (the plan was made for eight-wave workgroups: only version 2 has them)
     const bool cf = v2 && pl.geom.cf != 0;
-    const void *fn = cf ? (pl.waves == 8 ? (fused ? (const void *)&msda_fwd_f32_pquad2<true, 8, 1, true> : (const void *)&msda_fwd_f32_pquad2<false, 8, 1, true>)
-                                         : (fused ? (const void *)&msda_fwd_f32_pquad2<true, 4, 2, true> : (const void *)&msda_fwd_f32_pquad2<false, 4, 2, true>))
-                     : v2 ? (pl.waves == 8 ? (fused ? (const void *)&msda_fwd_f32_pquad2<true, 8, 1> : (const void *)&msda_fwd_f32_pquad2<false, 8, 1>)
-                           : pl.npass == 1 ? (fused ? (const void *)&msda_fwd_f32_pquad2<true, 4, 1> : (const void *)&msda_fwd_f32_pquad2<false, 4, 1>)
-                                           : (fused ? (const void *)&msda_fwd_f32_pquad2<true, 4, 2> : (const void *)&msda_fwd_f32_pquad2<false, 4, 2>))
-                     : D == 36 ? (fused ? pq_kernel_d36<true>(wide) : pq_kernel_d36<false>(wide))
-                               : (fused ? pq_kernel<true>(pl.npass, wide) : pq_kernel<false>(pl.npass, wide));
-    // the dynamic-LDS limit is a per-function, per-device attribute: cheap, set on every first (function, device)
-    struct Raised { const void *fn; int dev; };
-    static std::atomic<int> n_raised{0};
-    static Raised raised[64];
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    bool known = false;
-    const int n = n_raised.load(std::memory_order_acquire);
-    for (int i = 0; i < n && i < 64; ++i)
-        if (raised[i].fn == fn && raised[i].dev == dev) known = true;
-    if (!known) {
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return false;
-        static std::atomic_flag lock = ATOMIC_FLAG_INIT;
-        while (lock.test_and_set(std::memory_order_acquire)) {}
-        const int k = n_raised.load(std::memory_order_relaxed);
-        if (k < 64) {
-            raised[k] = Raised{fn, dev};
-            n_raised.store(k + 1, std::memory_order_release);
-        }
-        lock.clear(std::memory_order_release);
-    }
+    const KernelVariant kv = fused ? pquad_variant<true>(pl, D, wide, v2, cf) : pquad_variant<false>(pl, D, wide, v2, cf);
+    if (!raise_dynamic_lds_limit(kv.fn)) return false;
     pl.geom.trace = g_pq_trace.load(std::memory_order_relaxed);
     void *argv[] = {(void *)&da, (void *)&lt, (void *)&pl.geom};
-    *err = hipLaunchKernel(fn, dim3((unsigned)grid), dim3(64 * pl.waves), argv, pl.lds, stream);
-    note_kernel(cf ? (pl.waves == 8 ? (fused ? "msda_fwd_f32_pquad2<fused,8w,1p,cf>" : "msda_fwd_f32_pquad2<plain,8w,1p,cf>")
-                                    : (fused ? "msda_fwd_f32_pquad2<fused,4w,2p,cf>" : "msda_fwd_f32_pquad2<plain,4w,2p,cf>"))
-                : v2 ? (pl.waves == 8 ? (fused ? "msda_fwd_f32_pquad2<fused,8w,1p>" : "msda_fwd_f32_pquad2<plain,8w,1p>")
-                      : pl.npass == 1 ? (fused ? "msda_fwd_f32_pquad2<fused,4w,1p>" : "msda_fwd_f32_pquad2<plain,4w,1p>")
-                                      : (fused ? "msda_fwd_f32_pquad2<fused,4w,2p>" : "msda_fwd_f32_pquad2<plain,4w,2p>"))
-                   : D == 36 ? (fused ? "msda_fwd_f32_pquad<fused,D=36>" : "msda_fwd_f32_pquad<plain,D=36>")
-                             : (fused ? "msda_fwd_f32_pquad<fused>" : "msda_fwd_f32_pquad<plain>"));
+    *err = hipLaunchKernel(kv.fn, dim3((unsigned)grid), dim3(64 * pl.waves), argv, pl.lds, stream);
+    note_kernel(kv.name);
     return true;
 }
 
-int pquad_set_option(const char *name, int value)
-{
-    pq_opts_init();
-    for (int i = 0; i < kPoCount; ++i)
-        if (strcmp(name, kPqOptNames[i]) == 0) {
-            const int prev = g_pq_opt[i].exchange(value);
-            g_pq_epoch.fetch_add(1);
-            return prev;
-        }
-    return -1;
-}
+int pquad_set_option(const char *name, int value) { return g_pq_opt.set(name, value, -1); }
 
 void pquad_set_trace(unsigned long long *device_buffer) { g_pq_trace.store(device_buffer); }
 
