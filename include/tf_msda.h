@@ -31,7 +31,8 @@
  *     only.  What IS process-wide: (a) the kernel-selection knobs below (tf_msda_set_tiled / tf_msda_set_option and the
  *     environment variables they mirror) -- performance only, results identical up to fp32 summation order; they exist
  *     for A/B measurements, a deployment leaves them alone; (b) the per-thread last-HIP-error slot; (c) per-(function,
- *     device) one-time attribute calls (dynamic LDS above 64 KB).
+ *     device) one-time attribute calls (the dynamic-LDS limit of a kernel that may ask for more than 64 KB), and the
+ *     compute-unit count of the first device a call ran on, which the block-shape rules use for every device.
  *   - Return value: TF_MSDA_OK (0) or a negative tf_msda_status.  Never throws.
  *   - im2col_step of the reference API only chunks the batch (cu:44-66) and does not change results;
  *     this ABI has no such parameter.
@@ -96,11 +97,22 @@ int tf_msda_set_tiled(int mode);
  *   "quad_halo_y" / "quad_halo_x"   clamp of the data-adaptive windows around the tile footprint
  *   "quad_tile_h" / "quad_tile_w"   tile size in level-0 pixels (0 = search);  "quad_split"  staging rounds
  *   "direct9"       1 / 0: msda_fwd_f32_direct9 for D == 36 decoder calls (off: msda_fwd_f32_buf)
- *   "ffn_ti" "linln_ti" "linear_stream_ti"   row tiles per block of tf_ffn_fused_f32 / tf_linear_res_ln_f32 /
- *                   tf_linear_packed_f32 (include/tf_fused.h; 0 = per shape)
- *   "groups_ti"     row tiles per block of tf_linear_groups_f32 with fp16 pieces (1..3; 0 = by row count, the default)
- *   "wgrad_msplit"  chunks the row loop of tf_linear_wgrad_split_f32 is cut into (1..64; 0 = per shape, the default).  Unlike the
- *                   other knobs it changes the summation order of dw -- and the workspace tf_linear_wgrad_workspace_bytes asks for
+ * The knobs of the dense kernels (include/tf_fused.h) share one table: the value in force is the environment variable's
+ * at the first use (or the default), a value outside the range becomes the one in brackets -- from the variable and from
+ * this call alike --, a flag takes 0 / non-zero (from the variable: off only when it starts with '0'), and the call
+ * returns the value that was in force.
+ *   "ffn_ti"            TF_FFN_TI            1..3 [3], default 3   row tiles per block of tf_ffn_fused_f32
+ *   "ffn_tail_split"    TF_FFN_TAIL_SPLIT    flag, default 1       its rows behind the full rounds of 64-row blocks as 32-row blocks
+ *   "linln_ti"          TF_LINLN_TI          0..3 [0], default 0   row tiles per block of tf_linear_res_ln_f32 (0 = by row count)
+ *   "groups_ti"         -                    1..3 [0], default 0   row tiles per block of tf_linear_groups_f32 with fp16 pieces (0 = by row count)
+ *   "linear_stream_ti"  TF_LINEAR_STREAM_TI  1..4 [0], default 0   row tiles per block of tf_linear_packed_f32 / tf_conv_packed_f32 (0 = per shape)
+ *   "conv_halo"         TF_CONV_HALO         flag, default 1       the halo form of the stride-1 3 x 3 convolutions (0: the stream form)
+ *   "linear_dma"        TF_LINEAR_DMA        0..9 [0], default 0   the LDS-DMA GEMM behind tf_linear_packed_f32: 1..4 = a block shape, 9 = per call
+ *   "mha_mfma"          TF_MHA_MFMA          0..2 [1], default 1   tf_mha_core_f32: 1 = operands streamed into registers, 2 = K / V staged in
+ *                       LDS, 0 = the vector kernel.  (Until the knobs shared a table this one returned -1 before the first attention
+ *                       call, and an out-of-range TF_MHA_MFMA selected the LDS-staged kernel; both follow the common rule now.)
+ *   "wgrad_msplit"      -                    1..64 [0], default 0  chunks the row loop of tf_linear_wgrad_split_f32 is cut into (0 = per shape).
+ *                       Unlike the other knobs it changes the summation order of dw -- and the workspace tf_linear_wgrad_workspace_bytes asks for
  * Knobs of experiments that were measured and removed (linear_variant, linear_bufstore, linear_deep, linear_astat,
  * conv3_bufload, bwd_sorted2, tiled = 1) are unknown names now.
  */

@@ -1,0 +1,39 @@
+// TEST INFRASTRUCTURE: the few HIP runtime calls trackformer_amd/csrc/host_dispatch.h makes, as a host stub for
+// tests/host/lds_limit_threads.cpp -- a current device per thread that the test sets, and a hipFuncSetAttribute that counts
+// its calls per (function, device).  No GPU, no ROCm headers.
+#ifndef TF_TEST_HIP_STUB_H_
+#define TF_TEST_HIP_STUB_H_
+
+#include <atomic>
+
+typedef int hipError_t;
+constexpr hipError_t hipSuccess = 0;
+constexpr int hipFuncAttributeMaxDynamicSharedMemorySize = 8;
+struct hipDeviceProp_t {
+    int multiProcessorCount;
+};
+
+namespace hipstub {
+constexpr int kFunctions = 300, kDevices = 65;
+extern char functions[kFunctions];                          // &functions[i]: the "kernel" i
+extern std::atomic<int> raised[kFunctions][kDevices];       // hipFuncSetAttribute calls per (function, device)
+extern thread_local int device;
+}  // namespace hipstub
+
+inline hipError_t hipGetDevice(int *dev)
+{
+    *dev = hipstub::device;
+    return hipSuccess;
+}
+inline hipError_t hipGetDeviceProperties(hipDeviceProp_t *prop, int)
+{
+    prop->multiProcessorCount = 4;
+    return hipSuccess;
+}
+inline hipError_t hipFuncSetAttribute(const void *fn, int, int)
+{
+    hipstub::raised[static_cast<const char *>(fn) - hipstub::functions][hipstub::device].fetch_add(1, std::memory_order_relaxed);
+    return hipSuccess;
+}
+
+#endif  // TF_TEST_HIP_STUB_H_

@@ -44,9 +44,9 @@
 #include <stdint.h>
 #include <stdlib.h>
 
-#include <atomic>
 #include <type_traits>
 
+#include "host_dispatch.h"
 #include "msda_common.h"
 #include "split_product.h"
 #include "tf_fused.h"
@@ -399,13 +399,7 @@ int launch_ffn(const float *x, const u32x4 *w1, const float *b1, const u32x4 *w2
     constexpr size_t lds = ffn_lds_bytes<D>(TI, Split<SP>::NA);
     static_assert(lds <= 160 * 1024, "the two tiles do not fit the LDS of a CU");
     const void *fn = ln ? (const void *)&ffn_fused_kernel<SP, D, TI, true> : (const void *)&ffn_fused_kernel<SP, D, TI, false>;
-    static std::atomic<unsigned> raised[2];   // bit per device, per kernel
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev >= 32 || !(raised[ln ? 1 : 0].load() & (1u << dev))) {
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return TF_MSDA_ERR_LAUNCH;
-        if (dev < 32) raised[ln ? 1 : 0].fetch_or(1u << dev);
-    }
+    if (lds > 64 * 1024 && !tfm::raise_dynamic_lds_limit(fn)) return TF_MSDA_ERR_LAUNCH;
     const int blocks = (M + 32 * TI - 1) / (32 * TI);
     void *argv[] = {(void *)&x, (void *)&w1, (void *)&b1, (void *)&w2, (void *)&b2, (void *)&res,
                     (void *)&gamma, (void *)&beta, (void *)&eps, (void *)&y, (void *)&M, (void *)&F};
@@ -506,95 +500,10 @@ int launch_linln(const float *x, const u32x4 *w, const float *b, const float *re
     constexpr size_t lds = linln_lds_bytes<D>(TI, Split<SP>::NA);
     static_assert(lds <= 160 * 1024, "the activation tile does not fit the LDS of a CU");
     const void *fn = ln ? (const void *)&linear_res_ln_kernel<SP, D, TI, true> : (const void *)&linear_res_ln_kernel<SP, D, TI, false>;
-    if (lds > 64 * 1024) {
-        static std::atomic<unsigned> raised[2];   // bit per device, per kernel
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (dev >= 32 || !(raised[ln ? 1 : 0].load() & (1u << dev))) {
-            if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return TF_MSDA_ERR_LAUNCH;
-            if (dev < 32) raised[ln ? 1 : 0].fetch_or(1u << dev);
-        }
-    }
+    if (lds > 64 * 1024 && !tfm::raise_dynamic_lds_limit(fn)) return TF_MSDA_ERR_LAUNCH;
     const int blocks = (M + 32 * TI - 1) / (32 * TI);
     void *argv[] = {(void *)&x, (void *)&w, (void *)&b, (void *)&res, (void *)&gamma, (void *)&beta, (void *)&eps, (void *)&y, (void *)&M};
     return hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(Geo<D>::NT), argv, lds, s) == hipSuccess ? TF_MSDA_OK : TF_MSDA_ERR_LAUNCH;
-}
-
-std::atomic<int> g_linln_ti{-1};   // -1: TF_LINLN_TI or automatic (0)
-int linln_ti()
-{
-    int v = g_linln_ti.load(std::memory_order_relaxed);
-    if (v < 0) {
-        const char *e = getenv("TF_LINLN_TI");
-        v = e ? atoi(e) : 0;
-        if (v < 0 || v > 3) v = 0;
-        g_linln_ti.store(v);
-    }
-    return v;
-}
-
-std::atomic<int> g_groups_ti{0};   // tf_linear_groups_f32, fp16 pieces: row tiles per block (1..3); 0: by row count
-std::atomic<int> g_ffn_tail{-1};   // -1: TF_FFN_TAIL_SPLIT or the default (1): the rows behind the full rounds as 32-row blocks
-std::atomic<int> g_ffn_ti{-1};   // -1: TF_FFN_TI or the default (3)
-int ffn_ti()
-{
-    int v = g_ffn_ti.load(std::memory_order_relaxed);
-    if (v < 0) {
-        const char *e = getenv("TF_FFN_TI");
-        v = e ? atoi(e) : 3;
-        if (v < 1 || v > 3) v = 3;
-        g_ffn_ti.store(v);
-    }
-    return v;
-}
-
-}  // namespace
-
-namespace tfm {
-int ffn_tail_split()
-{
-    int v = g_ffn_tail.load(std::memory_order_relaxed);
-    if (v < 0) {
-        const char *e = getenv("TF_FFN_TAIL_SPLIT");
-        v = (e && e[0] == '0') ? 0 : 1;
-        g_ffn_tail.store(v);
-    }
-    return v;
-}
-int ffn_set_tail_split(int v)
-{
-    const int prev = ffn_tail_split();
-    g_ffn_tail.store(v ? 1 : 0);
-    return prev;
-}
-int ffn_set_ti(int v)
-{
-    const int prev = ffn_ti();
-    g_ffn_ti.store(v >= 1 && v <= 3 ? v : 3);
-    return prev;
-}
-int groups_set_ti(int v) { return g_groups_ti.exchange(v >= 1 && v <= 3 ? v : 0); }
-int linln_set_ti(int v)
-{
-    const int prev = linln_ti();
-    g_linln_ti.store(v >= 1 && v <= 3 ? v : 0);
-    return prev;
-}
-}  // namespace tfm
-
-namespace {
-
-int ffn_num_cus()
-{
-    static const int n = [] {
-        int dev = 0, cus = 256;
-        if (hipGetDevice(&dev) == hipSuccess) {
-            hipDeviceProp_t prop;
-            if (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
-        }
-        return cus;
-    }();
-    return n;
 }
 
 template <int SP, int D>
@@ -603,7 +512,7 @@ int dispatch_linln(const float *x, const u32x4 *w, const float *bias, const floa
 {
     // rows per block = 32 TI; automatic: few rows -> 32-row blocks (more of them), many -> 64 (two resident per CU with two
     // activation pieces; with three the 64-row tile is 99 KB of LDS: one block per CU)
-    const int forced = linln_ti();
+    const int forced = tfm::dense_knob(tfm::kKnobLinlnTi);
     // Three pieces: a 64-row tile is 99 KB of LDS -- one block per CU, rounds of `cus` blocks (348 blocks at the cfg-2 encoder: a
     // full round and a third of one).  32-row tiles (50 KB) keep three blocks resident per CU and the 695 blocks run as one
     // round: 26.2 us against 31.2 us with 64-row blocks (29.0 with the rows behind the full round split off as dispatch_ffn
@@ -632,10 +541,10 @@ int dispatch_ffn(const float *x, const u32x4 *w1, const float *b1, const u32x4 *
     // not depend on the block it is in): bit-identical.
     constexpr bool three_tiles = D == 256 && Split<SP>::NB == 2;   // 96 rows per block: two stored weight pieces only (with three the
                                                                    // ring of weight units leaves no room for a third row tile's accumulators)
-    const int want = ffn_ti();
+    const int want = tfm::dense_knob(tfm::kKnobFfnTi);
     const bool ti2 = want == 2 || (want >= 3 && !three_tiles);
-    if (ti2 && tfm::ffn_tail_split()) {
-        const int cus = ffn_num_cus();
+    if (ti2 && tfm::dense_knob(tfm::kKnobFfnTailSplit)) {
+        const int cus = tfm::num_cus();
         const long long per_round = 64LL * cus;
         const int main_rows = (int)(M / per_round * per_round), rem = M - main_rows;
         if (main_rows > 0 && rem > 0 && rem <= 32LL * cus) {
@@ -918,15 +827,7 @@ int launch_groups(const float *x, const float *x2, int M, const ProjGroups &pg, 
     static_assert(lds_max <= 160 * 1024, "the activation tile and the tables do not fit the LDS of a CU");
     const size_t lds = tile + 2 * 4 * (size_t)pg.ncols;
     const void *fn = (const void *)&linear_groups_kernel<SP, TI>;
-    if (lds_max > 64 * 1024) {
-        static std::atomic<unsigned> raised;   // bit per device
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (dev >= 32 || !(raised.load() & (1u << dev))) {
-            if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max) != hipSuccess) return TF_MSDA_ERR_LAUNCH;
-            if (dev < 32) raised.fetch_or(1u << dev);
-        }
-    }
+    if (lds_max > 64 * 1024 && !tfm::raise_dynamic_lds_limit(fn)) return TF_MSDA_ERR_LAUNCH;
     const int blocks = (M + 32 * TI - 1) / (32 * TI);
     void *argv[] = {(void *)&x, (void *)&x2, (void *)&M, (void *)&pg};
     return hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(256), argv, lds, s) == hipSuccess ? TF_MSDA_OK : TF_MSDA_ERR_LAUNCH;
@@ -971,7 +872,7 @@ extern "C" int tf_linear_groups_f32(const float *x, const float *x2, const tf_pr
     // 32 below -- the threshold of the other fused routes, NOT a measured crossover: only 22 223 rows were timed (there 32 / 64 /
     // 96 rows lie within 10 % of each other), and at 4096 rows 96-row blocks are 43 blocks on 256 CUs.  Option "groups_ti" forces it.
     if (sp == 3) return launch_groups<3, 1>(x, x2, (int)M, pg, s);
-    const int forced = g_groups_ti.load(std::memory_order_relaxed);
+    const int forced = tfm::dense_knob(tfm::kKnobGroupsTi);
     switch (forced ? forced : (M < 4096 ? 1 : 3)) {
     case 1: return launch_groups<16, 1>(x, x2, (int)M, pg, s);
     case 2: return launch_groups<16, 2>(x, x2, (int)M, pg, s);

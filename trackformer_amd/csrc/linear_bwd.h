@@ -290,8 +290,6 @@ wgrad_kernel(const float *__restrict__ dy, const float *__restrict__ x, const fl
     }
 }
 
-std::atomic<int> g_wgrad_msplit{0};   // 0: per shape
-
 struct WgradPlan {
     int msplit, spc;   // chunks of the row loop, slices of 32 rows per chunk
 };
@@ -302,7 +300,7 @@ inline WgradPlan wgrad_plan(long long M, int K, int N)
 {
     const int nslices = (int)((M + kWgSlice - 1) / kWgSlice);
     const int tiles = ((N + kWgTile - 1) / kWgTile) * ((K + kWgTile - 1) / kWgTile);
-    int ms = g_wgrad_msplit.load(std::memory_order_relaxed);
+    int ms = tfm::dense_knob(tfm::kKnobWgradMsplit);   // 0: per shape
     if (ms <= 0) {
         ms = 512 / tiles;
         if (ms > nslices / 4) ms = nslices / 4;
@@ -316,13 +314,6 @@ inline WgradPlan wgrad_plan(long long M, int K, int N)
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
-
-namespace tfm {
-int wgrad_msplit_set(int v)
-{
-    return g_wgrad_msplit.exchange(v >= 1 && v <= 64 ? v : 0);
-}
-}  // namespace tfm
 
 extern "C" int64_t tf_linear_grad_stats_workspace_bytes(int64_t M, int C, int role, int with_colsum)
 {
@@ -386,13 +377,7 @@ extern "C" int tf_linear_wgrad_split_f32(const float *dy, const float *x, const 
     else
         hipLaunchKernelGGL(wgrad_kernel<16>, grid, dim3(256), 0, s, dy, x, dy_scale2, x_scale2, out, (int)M, N, K, ktiles, p.spc);
     if (hipGetLastError() != hipSuccess) return TF_MSDA_ERR_LAUNCH;
-    if (p.msplit > 1) {
-        const long long nk4 = (long long)N * K / 4;
-        hipLaunchKernelGGL(stream_splitk_reduce_kernel, dim3((unsigned)((nk4 + 255) / 256)), dim3(256), 0, s, (const float *)out,
-                           (const float *)nullptr, (const float *)nullptr, dw, nk4, K / 4, p.msplit, 0);
-        if (hipGetLastError() != hipSuccess) return TF_MSDA_ERR_LAUNCH;
-    }
-    return TF_MSDA_OK;
+    return p.msplit > 1 ? launch_splitk_reduce(out, nullptr, nullptr, dw, (long long)N * K, K, p.msplit, 0, s) : TF_MSDA_OK;
 }
 
 // dx = dy . w through the stream GEMM: the block shapes of stream_dispatch by the output width alone (every shape gives the same bits:

@@ -32,9 +32,9 @@
 #include <stdint.h>
 #include <stdlib.h>
 
-#include <atomic>
 #include <type_traits>
 
+#include "host_dispatch.h"
 #include "msda_common.h"
 #include "split_product.h"
 #include "tf_fused.h"
@@ -946,33 +946,6 @@ conv3x3_halo_kernel(const float *__restrict__ X, const u32x4 *__restrict__ Wp, c
     }
 }
 
-int num_cus()
-{
-    static const int n = [] {
-        int dev = 0, cus = 256;
-        if (hipGetDevice(&dev) == hipSuccess) {
-            hipDeviceProp_t prop;
-            if (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
-        }
-        return cus;
-    }();
-    return n;
-}
-
-std::atomic<int> g_ti{-1};   // -1: TF_LINEAR_STREAM_TI or automatic (0)
-
-int forced_ti()
-{
-    int v = g_ti.load(std::memory_order_relaxed);
-    if (v < 0) {
-        const char *e = getenv("TF_LINEAR_STREAM_TI");
-        v = e ? atoi(e) : 0;
-        if (v < 1 || v > 4) v = 0;
-        g_ti.store(v);
-    }
-    return v;
-}
-
 // ---------------------------------------------------------------------------------------------------------------- host side
 struct StreamCall {
     const float *x;
@@ -985,6 +958,16 @@ struct StreamCall {
     float *workspace;   // split-K partial sums [pieces][M][N], or NULL
     int ksplit;         // pieces the K loop is cut into (1: none)
 };
+
+// the second pass of a split sum: out [count] = [relu](sum of the `pieces` partials [pieces][count] + bias + res), rows of `cols` floats
+int launch_splitk_reduce(const float *partials, const float *bias, const float *res, float *out, long long count, int cols, int pieces,
+                         int relu, hipStream_t s)
+{
+    const long long n4 = count / 4;
+    hipLaunchKernelGGL(stream_splitk_reduce_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, partials, bias, res, out, n4, cols / 4,
+                       pieces, relu);
+    return hipGetLastError() == hipSuccess ? TF_MSDA_OK : TF_MSDA_ERR_LAUNCH;
+}
 
 template <int SP, int TI, int TJ, int WC, bool CONV, bool XSC = false>
 int launch_stream(const StreamCall &c, hipStream_t s)
@@ -1006,13 +989,7 @@ int launch_stream(const StreamCall &c, hipStream_t s)
                        partial ? nullptr : c.bias, partial ? nullptr : c.res, out, c.M, c.K, c.N, mblocks, nblocks, partial ? 0 : c.relu,
                        kslices, c.cv);
     if (hipGetLastError() != hipSuccess) return TF_MSDA_ERR_LAUNCH;
-    if (partial) {
-        const long long mn4 = (long long)c.M * c.N / 4;
-        hipLaunchKernelGGL(stream_splitk_reduce_kernel, dim3((unsigned)((mn4 + 255) / 256)), dim3(256), 0, s, c.workspace, c.bias, c.res,
-                           c.y, mn4, c.N / 4, gz, c.relu);
-        if (hipGetLastError() != hipSuccess) return TF_MSDA_ERR_LAUNCH;
-    }
-    return TF_MSDA_OK;
+    return partial ? launch_splitk_reduce(c.workspace, c.bias, c.res, c.y, (long long)c.M * c.N, c.N, gz, c.relu, s) : TF_MSDA_OK;
 }
 
 // Block shape per call.  Columns: N <= 64 -> 64-column blocks (2 x 2 waves), N <= 128 -> 128 (4 waves side by side, one column
@@ -1023,20 +1000,20 @@ int launch_stream(const StreamCall &c, hipStream_t s)
 template <int SP, bool CONV>
 int stream_dispatch(const StreamCall &c, hipStream_t s)
 {
-    const int f = forced_ti();
+    const int f = tfm::dense_knob(tfm::kKnobLinearStreamTi);
     const long long pieces = c.ksplit > 1 ? c.ksplit : 1;
     if (c.N <= 64) {
-        const bool big = f ? f >= 2 : (long long)((c.M + 127) / 128) * pieces >= 2LL * num_cus();
+        const bool big = f ? f >= 2 : (long long)((c.M + 127) / 128) * pieces >= 2LL * tfm::num_cus();
         return big ? launch_stream<SP, 2, 1, 2, CONV>(c, s) : launch_stream<SP, 1, 1, 2, CONV>(c, s);
     }
     if (c.N <= 128) {
         // (round 5, measured and removed: 128 x 128 blocks as 2 x 2 waves of 64 x 64 -- half the LDS re-reads of the activations per
         // MFMA, twice the weight fragments per wave: 150.6 us against 146.9 at 131 072 rows, profiles/r05_conv3_tiles_2x2_waves.txt)
-        const bool big = f ? f >= 4 : (long long)((c.M + 127) / 128) * pieces >= 2LL * num_cus();
+        const bool big = f ? f >= 4 : (long long)((c.M + 127) / 128) * pieces >= 2LL * tfm::num_cus();
         return big ? launch_stream<SP, 4, 1, 4, CONV>(c, s) : launch_stream<SP, 2, 1, 4, CONV>(c, s);
     }
     if constexpr (CONV) {   // (three row tiles of the convolution form do not fit the register file with three pieces)
-        const bool big = f ? f >= 4 : (long long)((c.M + 127) / 128) * ((c.N + 255) / 256) * pieces >= 2LL * num_cus();
+        const bool big = f ? f >= 4 : (long long)((c.M + 127) / 128) * ((c.N + 255) / 256) * pieces >= 2LL * tfm::num_cus();
         return big ? launch_stream<SP, 4, 2, 4, CONV>(c, s) : launch_stream<SP, 2, 2, 4, CONV>(c, s);
     } else {
         // (fp16 pieces: three row tiles at every K -- 22 223 rows: 256 -> 1024 48.8 vs 51.3 us, 1024 -> 256 43.2 vs 50.5, 256 -> 256
@@ -1052,18 +1029,6 @@ int stream_dispatch(const StreamCall &c, hipStream_t s)
 
 // ---- the halo form: block shape per call (as stream_dispatch: 64 / 128 / 256 columns; 64-pixel patches, 128 where that still leaves
 // about two blocks per CU)
-std::atomic<int> g_halo{-1};   // -1: TF_CONV_HALO or the default (1)
-bool halo_enabled()
-{
-    int v = g_halo.load(std::memory_order_relaxed);
-    if (v < 0) {
-        const char *e = getenv("TF_CONV_HALO");
-        v = (e && e[0] == '0') ? 0 : 1;
-        g_halo.store(v);
-    }
-    return v != 0;
-}
-
 template <int SP, int TI, int TJ, int WC, bool MRG = false>
 int launch_halo(const StreamCall &c, hipStream_t s, const HaloMerge mg = HaloMerge{})
 {
@@ -1086,21 +1051,15 @@ int launch_halo(const StreamCall &c, hipStream_t s, const HaloMerge mg = HaloMer
                        partial ? nullptr : c.bias, partial ? nullptr : c.res, out, c.N, nblocks, (int)npatches, tiles_x, tiles_y,
                        partial ? 0 : c.relu, cslices, c.cv, mg);
     if (hipGetLastError() != hipSuccess) return TF_MSDA_ERR_LAUNCH;
-    if (partial) {
-        const long long mn4 = (long long)c.M * c.N / 4;
-        hipLaunchKernelGGL(stream_splitk_reduce_kernel, dim3((unsigned)((mn4 + 255) / 256)), dim3(256), 0, s, c.workspace, c.bias, c.res,
-                           c.y, mn4, c.N / 4, gz, c.relu);
-        if (hipGetLastError() != hipSuccess) return TF_MSDA_ERR_LAUNCH;
-    }
-    return TF_MSDA_OK;
+    return partial ? launch_splitk_reduce(c.workspace, c.bias, c.res, c.y, (long long)c.M * c.N, c.N, gz, c.relu, s) : TF_MSDA_OK;
 }
 
 template <int SP>
 int halo_dispatch(const StreamCall &c, hipStream_t s)
 {
-    const int f = forced_ti();
+    const int f = tfm::dense_knob(tfm::kKnobLinearStreamTi);
     const long long pieces = c.ksplit > 1 ? c.ksplit : 1;
-    const bool big = (long long)((c.M + 127) / 128) * ((c.N + 255) / 256) * pieces >= 2LL * num_cus();
+    const bool big = (long long)((c.M + 127) / 128) * ((c.N + 255) / 256) * pieces >= 2LL * tfm::num_cus();
     // (<= 32 output channels -- the mask head's lay4 / lay5: 32 / 16 at up to 200 x 334 pixels per query --: one column tile, the four
     // waves split the rows; the 64-column shapes leave two of the four waves multiplying padding)
     // 128-row blocks whatever the launch size: at Cin <= 64 a block's life is one or two slices -- cold halo, nine taps of weight
@@ -1122,21 +1081,8 @@ int halo_dispatch_merge(const StreamCall &c, hipStream_t s, const HaloMerge &mg)
     return launch_halo<SP, 2, 2, 4, true>(c, s, mg);
 }
 
-// ---- the LDS-DMA GEMM: shape per call.  g_dma: -1 = TF_LINEAR_DMA or the default, 0 = off (the stream form), 1..4 = a fixed shape
+// ---- the LDS-DMA GEMM: shape per call.  Knob linear_dma: 0 = off (the stream form), 1..4 = a fixed shape
 // (1: 128 x 128, 2 slices; 2: 128 x 64, 3 slices; 3: 128 x 128, 3 slices; 4: 256 x 128, 2 slices), 9 = per call shape
-std::atomic<int> g_dma{-1};
-int dma_mode()
-{
-    int v = g_dma.load(std::memory_order_relaxed);
-    if (v < 0) {
-        const char *e = getenv("TF_LINEAR_DMA");
-        v = e ? atoi(e) : 0;
-        if (v < 0 || v > 9) v = 0;
-        g_dma.store(v);
-    }
-    return v;
-}
-
 template <int SP, int TI, int TJ, int STAGES>
 int launch_dma(const StreamCall &c, hipStream_t s)
 {
@@ -1147,14 +1093,7 @@ int launch_dma(const StreamCall &c, hipStream_t s)
     const long long gx = (long long)((mblocks + 7) / 8) * 8 * nblocks;
     if (gx > 0x7fffffffLL) return TF_MSDA_ERR_BAD_DIMS;
     const void *fn = (const void *)&dma_gemm_kernel<SP, TI, TJ, STAGES>;
-    static std::atomic<unsigned long long> raised{0};   // bit d: device d has the dynamic-LDS attribute of THIS instantiation
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (!(raised.load(std::memory_order_acquire) & bit)) {
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return TF_MSDA_ERR_LAUNCH;
-        raised.fetch_or(bit, std::memory_order_release);
-    }
+    if (!tfm::raise_dynamic_lds_limit(fn)) return TF_MSDA_ERR_LAUNCH;
     hipLaunchKernelGGL((dma_gemm_kernel<SP, TI, TJ, STAGES>), dim3((unsigned)gx), dim3(kThreads), lds, s, c.x, c.wp, c.bias, c.res, c.y,
                        c.M, c.K, c.N, mblocks, nblocks, c.relu);
     return hipGetLastError() == hipSuccess ? TF_MSDA_OK : TF_MSDA_ERR_LAUNCH;
@@ -1173,27 +1112,6 @@ int dma_dispatch(int mode, const StreamCall &c, hipStream_t s)
 }
 
 }  // namespace
-
-namespace tfm {
-int linear_dma_set(int v)
-{
-    const int prev = dma_mode();
-    g_dma.store(v >= 0 && v <= 9 ? v : 0);
-    return prev;
-}
-int conv_halo_set(int v)
-{
-    const int prev = halo_enabled() ? 1 : 0;
-    g_halo.store(v != 0 ? 1 : 0);
-    return prev;
-}
-int linear_stream_set_ti(int v)
-{
-    const int prev = forced_ti();
-    g_ti.store(v >= 1 && v <= 4 ? v : 0);
-    return prev;
-}
-}  // namespace tfm
 
 template <bool CONV>
 int stream_dispatch_scheme(int sp, const StreamCall &c, hipStream_t s)
@@ -1279,7 +1197,7 @@ extern "C" int tf_linear_packed_f32(const float *x, const void *w_packed, const 
     if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(w_packed)) & 15) return TF_MSDA_ERR_BAD_DIMS;
     if ((long long)(M + 256) * N * 4 >= 0xC0000000LL) return TF_MSDA_ERR_BAD_DIMS;   // buffer-resource offsets (the caller keeps tf_linear_split_f32)
     StreamCall c{x, static_cast<const u32x4 *>(w_packed), bias, residual, y, (int)M, K, N, relu, false, StreamConv{}, nullptr, 1};
-    if (const int mode = dma_mode())   // the LDS-DMA GEMM (both operands global -> LDS by DMA, a ring of slices in flight)
+    if (const int mode = tfm::dense_knob(tfm::kKnobLinearDma))   // the LDS-DMA GEMM (both operands global -> LDS by DMA, a ring of slices in flight)
         if ((long long)M * K * 4 < 0xC0000000LL)
             return sp == 3 ? dma_dispatch<3>(mode, c, static_cast<hipStream_t>(stream)) : dma_dispatch<16>(mode, c, static_cast<hipStream_t>(stream));
     return stream_dispatch_scheme<false>(sp, c, static_cast<hipStream_t>(stream));
@@ -1293,7 +1211,7 @@ extern "C" int tf_conv_packed_f32(const float *x, const void *w_packed, const fl
     const int sp = split_scheme(terms);
     // (the stream form walks pairs of 32-deep slices: Cin % 64; the halo form -- stride-1 3 x 3 -- any number of them: Cin % 32, which
     // the mask head's lay2 (288 channels) and lay5 (32) need)
-    const bool halo = ks == 3 && stride == 1 && halo_enabled();
+    const bool halo = ks == 3 && stride == 1 && tfm::dense_knob(tfm::kKnobConvHalo);
     if (nimg <= 0 || hin <= 0 || win <= 0 || cin <= 0 || cout <= 0 || (cin % (halo ? 32 : 64)) != 0 || (stride != 1 && stride != 2) ||
         (ks != 1 && ks != 3) || sp == 0 || ksplit < 1 || ksplit > 64)
         return TF_MSDA_ERR_BAD_DIMS;

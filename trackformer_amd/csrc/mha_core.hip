@@ -23,9 +23,9 @@
 #include <float.h>
 #include <stdlib.h>
 
-#include <atomic>
 #include <stdint.h>
 
+#include "host_dispatch.h"
 #include "msda_common.h"
 #include "tf_fused.h"
 #include "tf_msda.h"
@@ -523,16 +523,7 @@ mha_mfma_stream_kernel(const float *__restrict__ q, const float *__restrict__ k,
     }
 }
 
-std::atomic<int> g_mha_mfma{-1};   // -1: TF_MHA_MFMA from the environment on first use (default on); 0 / 1: set by tf_msda_set_option("mha_mfma")
-
 }  // namespace
-
-namespace tfm {
-int mha_set_mfma(int v)   // 1: operands streamed into registers (default), 2: K / V staged in LDS, 0: the vector kernel
-{
-    return g_mha_mfma.exchange(v < 0 || v > 2 ? 1 : v);
-}
-}  // namespace tfm
 
 extern "C" int tf_mha_core_f32(const float *q, const float *k, const float *v, float *out, const unsigned char *key_mask,
                                int N, int Lq, int Lk, int H, int D, int ldq, int ldk, int ldv, int ldo, float scale,
@@ -546,12 +537,7 @@ extern "C" int tf_mha_core_f32(const float *q, const float *k, const float *v, f
     if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k) | reinterpret_cast<uintptr_t>(v) |
          reinterpret_cast<uintptr_t>(out)) & 15)
         return TF_MSDA_ERR_BAD_DIMS;
-    int use_mfma = g_mha_mfma.load(std::memory_order_relaxed);
-    if (use_mfma < 0) {
-        const char *e = getenv("TF_MHA_MFMA");
-        use_mfma = e == nullptr ? 1 : atoi(e);
-        g_mha_mfma.store(use_mfma);
-    }
+    const int use_mfma = tfm::dense_knob(tfm::kKnobMhaMfma);   // 1: operands streamed into registers (default), 2: K / V staged in LDS, 0: the vector kernel
     const size_t budget = 150 * 1024;
     if (use_mfma == 1 && (D == 16 || D == 32 || D == 36 || D == 64)) {
         // K and V straight into the operand registers, the score tiles in the accumulators; LDS: the weights (rows 4 floats
@@ -568,17 +554,7 @@ extern "C" int tf_mha_core_f32(const float *q, const float *k, const float *v, f
             case 36: fns = one ? (const void *)&mha_mfma_stream_kernel<36, 1> : (const void *)&mha_mfma_stream_kernel<36, 2>; break;
             default: fns = one ? (const void *)&mha_mfma_stream_kernel<64, 1> : (const void *)&mha_mfma_stream_kernel<64, 2>; break;
             }
-            if (lds > 64 * 1024) {
-                static int raised_stream[8] = {0};   // per kernel and device; benign race
-                int dev = 0;
-                (void)hipGetDevice(&dev);
-                int &mask = raised_stream[(D == 16 ? 0 : D == 32 ? 1 : D == 36 ? 2 : 3) * 2 + (one ? 0 : 1)];
-                if (dev >= 31 || !(mask & (1 << dev))) {
-                    if (hipFuncSetAttribute(fns, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-                        return TF_MSDA_ERR_LAUNCH;
-                    if (dev < 31) mask |= 1 << dev;
-                }
-            }
+            if (lds > 64 * 1024 && !tfm::raise_dynamic_lds_limit(fns)) return TF_MSDA_ERR_LAUNCH;
             const dim3 grids((unsigned)((Lq + TQ - 1) / TQ), (unsigned)H, (unsigned)N);
             void *args[] = {(void *)&q, (void *)&k, (void *)&v, (void *)&out, (void *)&key_mask, (void *)&Lq, (void *)&Lk, (void *)&ldq,
                             (void *)&ldk, (void *)&ldv, (void *)&ldo, (void *)&scale, (void *)&lkp};
@@ -605,17 +581,7 @@ extern "C" int tf_mha_core_f32(const float *q, const float *k, const float *v, f
             const size_t lds = (size_t)(two ? 2 : 1) * kc * dp * sizeof(float) + fixed;
             const void *fnm = D == 16 ? (const void *)&mha_mfma_kernel<16> : D == 32 ? (const void *)&mha_mfma_kernel<32>
                               : D == 36 ? (const void *)&mha_mfma_kernel<36> : (const void *)&mha_mfma_kernel<64>;
-            if (lds > 64 * 1024) {
-                static int raised_mfma[4] = {0, 0, 0, 0};   // per kernel and device; benign race
-                int dev = 0;
-                (void)hipGetDevice(&dev);
-                int &mask = raised_mfma[D == 16 ? 0 : D == 32 ? 1 : D == 36 ? 2 : 3];
-                if (dev >= 31 || !(mask & (1 << dev))) {
-                    if (hipFuncSetAttribute(fnm, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-                        return TF_MSDA_ERR_LAUNCH;
-                    if (dev < 31) mask |= 1 << dev;
-                }
-            }
+            if (lds > 64 * 1024 && !tfm::raise_dynamic_lds_limit(fnm)) return TF_MSDA_ERR_LAUNCH;
             const dim3 gridm((unsigned)((Lq + TQ - 1) / TQ), (unsigned)H, (unsigned)N);
             void *argm[] = {(void *)&q, (void *)&k, (void *)&v, (void *)&out, (void *)&key_mask, (void *)&Lq, (void *)&Lk, (void *)&ldq,
                             (void *)&ldk, (void *)&ldv, (void *)&ldo, (void *)&scale, (void *)&lkp, (void *)&kc, (void *)&two};
@@ -642,17 +608,7 @@ extern "C" int tf_mha_core_f32(const float *q, const float *k, const float *v, f
     case 16: fn = (const void *)&mha_core_kernel<16>; break;
     default: return TF_MSDA_ERR_BAD_DIMS;   // head dimensions 16, 32, 36, 64
     }
-    if (lds > 64 * 1024) {
-        static int raised_dev_mask[17] = {0};   // per kernel (index D / 4) and device; benign race
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        int &mask = raised_dev_mask[D / 4];
-        if (dev >= 31 || !(mask & (1 << dev))) {
-            if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-                return TF_MSDA_ERR_LAUNCH;
-            if (dev < 31) mask |= 1 << dev;
-        }
-    }
+    if (lds > 64 * 1024 && !tfm::raise_dynamic_lds_limit(fn)) return TF_MSDA_ERR_LAUNCH;
     const dim3 grid((unsigned)((Lq + TQ - 1) / TQ), (unsigned)H, (unsigned)N);
     void *argv[] = {(void *)&q, (void *)&k, (void *)&v, (void *)&out, (void *)&key_mask, (void *)&Lq, (void *)&Lk, (void *)&ldq,
                     (void *)&ldk, (void *)&ldv, (void *)&ldo, (void *)&scale, (void *)&lk_pad, (void *)&kc};

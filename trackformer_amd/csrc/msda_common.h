@@ -64,23 +64,6 @@ bool launch_pquad(bool fused, const DirectArgs &da, const LevelTable &lt, int N,
 int pquad_set_option(const char *name, int value);   // -1: unknown name, else the previous value
 void pquad_set_trace(unsigned long long *device_buffer);
 
-// ffn_fused.hip: row tiles per block of tf_ffn_fused_f32 (1..3, default 3); returns the previous value
-int ffn_set_ti(int v);
-int ffn_tail_split();            // tf_ffn_fused_f32: the rows behind the full rounds of 64-row blocks go to 32-row blocks (0 / 1, default 1)
-int ffn_set_tail_split(int v);
-int linln_set_ti(int v);   // tf_linear_res_ln_f32 (1..3; 0 = by row count)
-int groups_set_ti(int v);  // tf_linear_groups_f32, fp16 pieces (1..3; 0 = by row count)
-// linear_stream.hip: row tiles per block of tf_linear_packed_f32 (2..4; 0 = per shape); returns the previous value
-int linear_stream_set_ti(int v);
-// linear_stream.hip: 1 = the halo form of the stride-1 3 x 3 convolutions (default), 0 = the stream form; returns the previous value
-int conv_halo_set(int v);
-// linear_stream.hip: the LDS-DMA GEMM behind tf_linear_packed_f32: 0 = off (the stream form), 1..4 = a fixed block shape, 9 = per call
-int linear_dma_set(int v);
-// linear_stream.hip (linear_bwd.h): chunks the row loop of tf_linear_wgrad_split_f32 is cut into (1..64; 0 = per shape); returns the previous value
-int wgrad_msplit_set(int v);
-// mha_core.hip: 1 = the matrix-core kernel (default), 0 = the vector kernel of round 4; returns the previous value
-int mha_set_mfma(int v);
-
 }  // namespace tfm
 
 #endif  // TF_MSDA_COMMON_H_

@@ -1,6 +1,6 @@
 // trackformer_amd/csrc/msda_dispatch.h -- the host-side dispatch layer of the MSDeformAttn kernels, shared by
-// msda_hip.hip and msda_pquad.hip (host code only): kernel variants, option tables, 0/1 environment flags, the
-// dynamic-LDS limit, the tile-plan memo and the tile counting function.
+// msda_hip.hip and msda_pquad.hip (host code only): option tables, the tile-plan memo and the tile counting function,
+// on top of the family-neutral host_dispatch.h (kernel variants, 0/1 environment flags, the dynamic-LDS limit).
 #ifndef TF_MSDA_DISPATCH_H_
 #define TF_MSDA_DISPATCH_H_
 
@@ -13,24 +13,11 @@
 #include <atomic>
 #include <mutex>
 
+#include "host_dispatch.h"
 #include "msda_common.h"
 
 namespace tfm {
 
-// A kernel and the name tf_msda_last_kernel reports for it, chosen together by one selection function per kernel
-// family: the launch and note_kernel use the same variant.  `name` is a string literal.
-struct KernelVariant {
-    const void *fn;
-    const char *name;
-};
-
-// 0/1 environment flag: unset -> dflt, set -> off only when its first character is '0'.  (Read once by the caller:
-// `static const bool on = env_flag(...)`.)
-inline bool env_flag(const char *name, bool dflt)
-{
-    const char *e = getenv(name);
-    return e ? e[0] != '0' : dflt;
-}
 // TF_MSDA_VERBOSE: on when set, to whatever value
 inline bool msda_verbose()
 {
@@ -56,46 +43,6 @@ inline long long tile_max_queries(const LevelTable &lt, int L, int th, int tw)
             if (nq > max_nq) max_nq = nq;
         }
     return max_nq;
-}
-
-// The dynamic-LDS limit (hipFuncAttributeMaxDynamicSharedMemorySize) is an attribute of a function ON A DEVICE: raised
-// once per (function, current device).  One slot per function with a bit per device (64 devices; the slots outnumber
-// the ~60 instantiations that need it); a hit reads two atomics, the first use of a pair takes the lock.
-constexpr int kLdsLimitSlots = 128;
-struct LdsLimitSlot {
-    std::atomic<const void *> fn{nullptr};
-    std::atomic<unsigned long long> devs{0};
-};
-// The slot of `fn` (slots fill in order and are never released), or null.
-inline LdsLimitSlot *lds_limit_find(LdsLimitSlot *slots, const void *fn)
-{
-    for (int i = 0; i < kLdsLimitSlots; ++i) {
-        const void *f = slots[i].fn.load(std::memory_order_acquire);
-        if (f == fn) return &slots[i];
-        if (!f) break;
-    }
-    return nullptr;
-}
-inline bool raise_dynamic_lds_limit(const void *fn)
-{
-    static LdsLimitSlot slots[kLdsLimitSlots];
-    static std::mutex mu;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
-    const unsigned long long bit = 1ull << dev;
-    LdsLimitSlot *s = lds_limit_find(slots, fn);
-    if (s && (s->devs.load(std::memory_order_acquire) & bit)) return true;
-    std::lock_guard<std::mutex> guard(mu);
-    s = lds_limit_find(slots, fn);
-    if (s && (s->devs.load(std::memory_order_relaxed) & bit)) return true;
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return false;
-    for (int i = 0; !s && i < kLdsLimitSlots; ++i)
-        if (!slots[i].fn.load(std::memory_order_relaxed)) {
-            s = &slots[i];
-            s->fn.store(fn, std::memory_order_release);
-        }
-    if (s) s->devs.fetch_or(bit, std::memory_order_release);
-    return true;
 }
 
 // Process-wide integer knobs of one kernel family: set by name (tf_msda_set_option) or, before the first use, from a

@@ -2099,6 +2099,53 @@ int backward_impl(const T *value, const int64_t *shapes_host, const int64_t *sha
 
 namespace tfm {
 void note_kernel(const char *name) { g_last_kernel = name; }
+
+// The knobs of the dense kernels (host_dispatch.h), in the order of DenseKnob.  A flag takes 0 / non-zero (from the environment:
+// env_flag); a range knob takes lo..hi and turns everything else, from the setter or from the environment, into `other`.
+struct DenseKnobDesc {
+    const char *name, *env;   // tf_msda_set_option; the variable read at the first use, or null
+    int dflt;
+    bool flag;
+    int lo, hi, other;
+};
+constexpr DenseKnobDesc kDenseKnobs[kKnobCount] = {
+    {"ffn_ti", "TF_FFN_TI", 3, false, 1, 3, 3},
+    {"ffn_tail_split", "TF_FFN_TAIL_SPLIT", 1, true, 0, 1, 0},
+    {"linln_ti", "TF_LINLN_TI", 0, false, 0, 3, 0},
+    {"groups_ti", nullptr, 0, false, 1, 3, 0},
+    {"linear_stream_ti", "TF_LINEAR_STREAM_TI", 0, false, 1, 4, 0},
+    {"conv_halo", "TF_CONV_HALO", 1, true, 0, 1, 0},
+    {"linear_dma", "TF_LINEAR_DMA", 0, false, 0, 9, 0},
+    {"mha_mfma", "TF_MHA_MFMA", 1, false, 0, 2, 1},
+    {"wgrad_msplit", nullptr, 0, false, 1, 64, 0},
+};
+static std::atomic<int> g_dense_knob[kKnobCount];   // the value in force + 1; 0: not read yet
+
+static int dense_knob_accept(const DenseKnobDesc &d, int v) { return d.flag ? v != 0 : (v >= d.lo && v <= d.hi ? v : d.other); }
+
+int dense_knob(DenseKnob k)
+{
+    int cur = g_dense_knob[k].load(std::memory_order_relaxed);
+    if (cur == 0) {   // first use: the environment or the default, unless a setter got there first
+        const DenseKnobDesc &d = kDenseKnobs[k];
+        int v = d.dflt;
+        if (d.env && d.flag) v = env_flag(d.env, d.dflt != 0);
+        else if (const char *e = d.env ? getenv(d.env) : nullptr) v = dense_knob_accept(d, atoi(e));
+        if (g_dense_knob[k].compare_exchange_strong(cur, v + 1)) cur = v + 1;
+    }
+    return cur - 1;
+}
+
+int dense_knob_set(const char *name, int v, int unknown)
+{
+    for (int k = 0; k < kKnobCount; ++k)
+        if (strcmp(name, kDenseKnobs[k].name) == 0) {
+            const int prev = dense_knob((DenseKnob)k);
+            g_dense_knob[k].store(dense_knob_accept(kDenseKnobs[k], v) + 1);
+            return prev;
+        }
+    return unknown;
+}
 }  // namespace tfm
 
 // ---------------------------------------------------------------------------------------------
@@ -2143,20 +2190,11 @@ int tf_msda_set_option(const char *name, int value)
     if (strcmp(name, "tiled") == 0) return tf_msda_set_tiled(value);
     if (strncmp(name, "quad_", 5) == 0) return g_quad_opt.set(name, value);
     if (strcmp(name, "direct9") == 0) return g_direct9.exchange(value < 0 ? -1 : (value ? 1 : 0));
-    if (strcmp(name, "ffn_ti") == 0) return ffn_set_ti(value);
-    if (strcmp(name, "ffn_tail_split") == 0) return ffn_set_tail_split(value);
-    if (strcmp(name, "linln_ti") == 0) return linln_set_ti(value);
-    if (strcmp(name, "groups_ti") == 0) return groups_set_ti(value);
-    if (strcmp(name, "linear_stream_ti") == 0) return linear_stream_set_ti(value);
-    if (strcmp(name, "conv_halo") == 0) return conv_halo_set(value);
-    if (strcmp(name, "linear_dma") == 0) return linear_dma_set(value);
-    if (strcmp(name, "mha_mfma") == 0) return mha_set_mfma(value);
-    if (strcmp(name, "wgrad_msplit") == 0) return wgrad_msplit_set(value);
     if (strncmp(name, "pquad", 5) == 0) {
         const int prev = pquad_set_option(name, value);
         return prev == -1 ? INT_MIN : prev;
     }
-    return INT_MIN;
+    return dense_knob_set(name, value, INT_MIN);
 }
 
 int tf_msda_forward_fused_f32(const float *value, const int64_t *shapes_hw_host,

@@ -805,20 +805,6 @@ struct PqPlan {
     int waves;
 };
 
-int pq_num_cus()
-{
-    static const int n = [] {
-        int dev = 0, cus = 256;
-        if (hipGetDevice(&dev) == hipSuccess) {
-            hipDeviceProp_t prop;
-            if (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-                cus = prop.multiProcessorCount;
-        }
-        return cus;
-    }();
-    return n;
-}
-
 bool pq_plan(const LevelTable &lt, int L, int M, int N, int D, PqPlan *out)
 {
     int o[kPoCount];
@@ -845,7 +831,7 @@ bool pq_plan(const LevelTable &lt, int L, int M, int N, int D, PqPlan *out)
         return memo.ok;
     }
     const long long cap_q = (long long)(16 * waves) * npass;
-    const long long slots = (long long)pq_num_cus() * wgs;
+    const long long slots = (long long)num_cus() * wgs;
     int bth = 0, btw = 0;
     if (o[kPoTileH] > 0 && o[kPoTileW] > 0) {
         const long long nq = tile_max_queries(lt, L, o[kPoTileH], o[kPoTileW]);
@@ -889,7 +875,7 @@ bool pq_plan(const LevelTable &lt, int L, int M, int N, int D, PqPlan *out)
     r.geom.cap_rows = cap_rows;
     r.lds = (size_t)kPqHdrBytes + (size_t)(2 + cap_rows) * rowb + (D == 36 ? 1024 : 0);
     r.geom.skew = o[kPoSkew];
-    r.geom.cus = pq_num_cus();
+    r.geom.cus = num_cus();
     r.geom.headmix = (o[kPoHeadMix] == 1 || (o[kPoHeadMix] == 2 && M % 2 == 0)) ? o[kPoHeadMix] : 0;
     r.geom.prio = (o[kPoPrio] == 1 || o[kPoPrio] == 2) ? o[kPoPrio] : 0;
     r.geom.store = (o[kPoStore] >= 0 && o[kPoStore] <= 3) ? o[kPoStore] : 0;
@@ -949,7 +935,7 @@ bool launch_pquad(bool fused, const DirectArgs &da, const LevelTable &lt, int N,
     PqPlan pl;
     if (!pq_plan(lt, da.L, da.M, N, D, &pl)) return false;
     if (D == 36 && pl.npass != 2) return false;
-    long long grid = (long long)pq_num_cus() * pl.wgs;
+    long long grid = (long long)num_cus() * pl.wgs;
     if (grid > pl.geom.n_items) grid = pl.geom.n_items;
     // 16-byte loads of the points need 16-byte aligned rows
     bool wide = pl.wide;
