@@ -72,6 +72,9 @@ EXPORTED_SYMBOLS = (
     "tf_set_criterion_fwd_f32",
     "tf_set_criterion_bwd_f32",
     "tf_match_cost_f32",
+    "tf_mask_loss_workspace_bytes",
+    "tf_mask_loss_fwd_f32",
+    "tf_mask_loss_bwd_f32",
     "tf_linear_split_add_f32",
     "tf_ffn_fused_f32",
     "tf_linear_res_ln_f32",
@@ -81,7 +84,7 @@ EXPORTED_SYMBOLS = (
     "tf_nms_host_f32",
 )
 
-ABI_VERSION = 8   # 8: tf_set_criterion_fwd / _bwd, tf_match_cost (7: tf_add_layernorm_train / _bwd; 6: tf_msda_fused_prologue / _backward_epilogue; 5: tf_linear_grad_stats / wgrad / dgrad; 4: tf_msda_backward_det_* and TF_MSDA_ERR_WORKSPACE; 3: the split-product entry points take w_lo / w_scale / terms)
+ABI_VERSION = 9   # 9: tf_mask_loss_workspace_bytes / _fwd / _bwd (8: tf_set_criterion_fwd / _bwd, tf_match_cost; 7:tf_add_layernorm_train / _bwd; 6: tf_msda_fused_prologue / _backward_epilogue; 5: tf_linear_grad_stats / wgrad / dgrad; 4: tf_msda_backward_det_* and TF_MSDA_ERR_WORKSPACE; 3: the split-product entry points take w_lo / w_scale / terms)
 
 _lib = None
 
@@ -227,6 +230,12 @@ def lib():
     L.tf_set_criterion_bwd_f32.argtypes = [vp] * 8 + [ci] * 5 + [cf, cf, cf, vp]
     L.tf_match_cost_f32.restype = ci
     L.tf_match_cost_f32.argtypes = [vp] * 5 + [i64, ci, ci] + [cf] * 5 + [vp]
+    L.tf_mask_loss_workspace_bytes.restype = i64
+    L.tf_mask_loss_workspace_bytes.argtypes = [ci, ci, ci]
+    L.tf_mask_loss_fwd_f32.restype = ci
+    L.tf_mask_loss_fwd_f32.argtypes = [vp] * 7 + [i64] + [ci] * 7 + [cf, cf, cf, vp]
+    L.tf_mask_loss_bwd_f32.restype = ci
+    L.tf_mask_loss_bwd_f32.argtypes = [vp] * 7 + [ci] * 7 + [cf, cf, cf, vp]
     L.tf_conv_packed_f32.restype = ci
     L.tf_conv_packed_f32.argtypes = [vp, vp, vp, vp, vp, vp] + [ci] * 10 + [vp]
     L.tf_mha_core_f32.restype = ci

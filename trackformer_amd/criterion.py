@@ -68,7 +68,7 @@ def set_layers_at_once(on):
 # THE SET CRITERION AND THE MATCHING COST) instead of _layers_at_once's several dozen.  The focal term is evaluated in its stable
 # form there, so the small elements of the loss and their gradients are accurate where the fp32 `1 - sigmoid(x)` of
 # sigmoid_focal_loss has lost them; the sums agree to fp32 rounding.  NOT covered (today's path): the two-stage `enc_outputs` losses,
-# masks (final layer, torch), the non-focal cross-entropy, unequal match counts, anything not fp32 on the device.  OFF by default:
+# masks (final layer: torch, or set_fused_masks below), the non-focal cross-entropy, unequal match counts, anything not fp32 on the device.  OFF by default:
 # whether it is faster inside a training step is a measurement (tools/bench_criterion.py, profiles/criterion_fused_bench.json).
 _fused = None    # None: follow TF_CRITERION_FUSED (unset: off)
 _fused_counts = {"own": 0, "torch": 0}
@@ -97,6 +97,56 @@ def fused_counts(reset=False):
         for k in _fused_counts:
             _fused_counts[k] = 0
     return out
+
+
+# THE FUSED MASK LOSSES (opt-in, a switch of its own: set_fused keeps meaning what it meant): with the switch on and fp32 contiguous
+# pred_masks on the device, SetCriterion.loss_masks -- reached from the stacked and from the looped path -- is fused.mask_losses
+# (include/tf_fused.h: THE MASK LOSSES; csrc/mask_loss.h): the bilinear upsampling, the focal and the dice loss in two launches forward
+# and one backward, the targets read as bytes, no [n, H, W] fp32 tensor in either direction, every sum in fp64 in a fixed order
+# (bit-identical from run to run) and the focal term in the stable form of the fused criterion.  NOT covered (today's lines): anything
+# not fp32 / contiguous / on the device, targets smaller than the predictions.  OFF by default (tools/bench_mask_losses.py,
+# profiles/mask_losses_bench.json).
+_fused_masks = None    # None: follow TF_CRITERION_FUSED_MASKS (unset: off)
+_fused_mask_counts = {"own": 0, "torch": 0}
+
+
+def fused_masks_enabled():
+    if _fused_masks is not None:
+        return _fused_masks
+    return os.environ.get("TF_CRITERION_FUSED_MASKS", "0") not in ("", "0")
+
+
+def set_fused_masks(on):
+    """Switch the fused mask losses on or off (process-wide; None: follow TF_CRITERION_FUSED_MASKS again); returns the previous
+    setting."""
+    global _fused_masks
+    prev = fused_masks_enabled()
+    _fused_masks = None if on is None else bool(on)
+    return fused._switched(prev, fused_masks_enabled())
+
+
+def fused_mask_counts(reset=False):
+    """How many SetCriterion.loss_masks calls with the switch on ran the library's own kernels ("own") and how many kept today's lines
+    ("torch")."""
+    out = dict(_fused_mask_counts)
+    if reset:
+        for k in _fused_mask_counts:
+            _fused_mask_counts[k] = 0
+    return out
+
+
+def build_mask_pairs(indices, num_queries, tgt_stride):
+    """The matcher's host-side pairs of the final layer -> (pair_src int32 [n] = b * Q + q, pair_tgt int32 [n] = b * tgt_stride + t: the
+    row of the padded target stack [B, tgt_stride, H, W] seen as [B * tgt_stride, H, W], row_pair int32 [B * Q] = the pair of each
+    prediction or -1) as numpy arrays, the pairs in the order loss_masks concatenates them.  indices[b] = (query indices, target
+    indices)."""
+    src = [np.asarray(s, dtype=np.int64) + b * num_queries for b, (s, _) in enumerate(indices)]
+    tgt = [np.asarray(t, dtype=np.int64) + b * tgt_stride for b, (_, t) in enumerate(indices)]
+    pair_src = np.concatenate(src).astype(np.int32) if src else np.zeros(0, np.int32)
+    pair_tgt = np.concatenate(tgt).astype(np.int32) if tgt else np.zeros(0, np.int32)
+    row_pair = np.full(len(indices) * num_queries, -1, dtype=np.int32)
+    row_pair[pair_src] = np.arange(pair_src.size, dtype=np.int32)
+    return pair_src, pair_tgt, row_pair
 
 
 def build_tgt_of(all_indices, sizes, num_queries):
@@ -206,6 +256,11 @@ class SetCriterion(nn.Module):
         return {'loss_bbox': loss_bbox.sum() / num_boxes, 'loss_giou': loss_giou.sum() / num_boxes}
 
     def loss_masks(self, outputs, targets, indices, num_boxes):
+        if fused_masks_enabled():
+            out = self._loss_masks_fused(outputs, targets, indices, num_boxes)
+            _fused_mask_counts["own" if out is not None else "torch"] += 1
+            if out is not None:
+                return out
         src_idx = self._get_src_permutation_idx(indices)
         tgt_idx = self._get_tgt_permutation_idx(indices)
         src_masks = outputs["pred_masks"]
@@ -216,6 +271,26 @@ class SetCriterion(nn.Module):
         target_masks = target_masks[tgt_idx].flatten(1)
         return {"loss_mask": sigmoid_focal_loss(src_masks, target_masks, num_boxes),
                 "loss_dice": dice_loss(src_masks, target_masks, num_boxes)}
+
+    def _loss_masks_fused(self, outputs, targets, indices, num_boxes):
+        """loss_masks through fused.mask_losses: 0-d views of one [2] tensor, or None when the kernels do not take the tensors (the
+        caller keeps today's lines).  The padded target stack stays bool; the host builds the three index arrays with numpy from the
+        matcher's host-side pairs and uploads them in ONE copy."""
+        src_masks = outputs["pred_masks"]
+        if not (src_masks.is_cuda and src_masks.dim() == 4):
+            return None
+        target_masks, _ = nested_tensor_from_tensor_list([t["masks"] for t in targets]).decompose()
+        if target_masks.dim() != 4 or target_masks.shape[0] != src_masks.shape[0]:
+            return None
+        per_image = target_masks.shape[1]
+        target_masks = target_masks.flatten(0, 1)                        # [B * per_image, H, W]: a view of the padded stack
+        if not fused.mask_losses_applies(src_masks, target_masks):
+            return None
+        pair_src, pair_tgt, row_pair = build_mask_pairs(indices, src_masks.shape[1], per_image)
+        n = pair_src.size
+        both = torch.from_numpy(np.concatenate([pair_src, pair_tgt, row_pair])).to(src_masks.device, non_blocking=True)
+        out = fused.mask_losses(src_masks, target_masks, both[:n], both[n:2 * n], 0.25, 2.0, num_boxes, row_pair=both[2 * n:])
+        return {"loss_mask": out[0], "loss_dice": out[1]}
 
     def _layers_at_once(self, layer_outputs, targets, all_indices, num_boxes):
         """The class (focal), cardinality and box losses of the final + auxiliary decoder layers computed TOGETHER (round 6): the

@@ -4,7 +4,11 @@ csrc/criterion.h), re-exported as fused.set_criterion / fused.match_cost / fused
 The losses of the stacked decoder layers (criterion.SetCriterion._layers_at_once: several dozen library launches forward, as many again
 in the backward) in ONE launch each way, and the matcher's focal cost matrix in one.  The switches live with their callers --
 criterion.set_fused() / TF_CRITERION_FUSED=1 and matcher.set_fused_cost() / TF_MATCHER_FUSED_COST=1, both OFF by default --; the
-functions here are the plain operators."""
+functions here are the plain operators.
+
+The mask losses of the matched pairs (SetCriterion.loss_masks: a bilinear upsampling to the padded image size and about 25 element-wise
+passes over [n, H, W] fp32 tensors) are mask_losses / mask_losses_applies below (include/tf_fused.h: THE MASK LOSSES; csrc/mask_loss.h),
+behind criterion.set_fused_masks() / TF_CRITERION_FUSED_MASKS=1, OFF by default."""
 import torch
 
 from . import _cabi
@@ -119,3 +123,77 @@ def match_cost(logits, boxes, tgt_ids, tgt_bbox, w_class, w_bbox, w_giou, alpha,
                                            _stream(logits.device))
     _cabi.check(rc, "tf_match_cost_f32")
     return cost
+
+
+# ---- THE MASK LOSSES (include/tf_fused.h: THE MASK LOSSES; csrc/mask_loss.h) -----------------------------------------------------------
+class _MaskLosses(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred_masks, tgt, pair_src, pair_tgt, row_pair, alpha, gamma, num_boxes):
+        B, Q, h, w = pred_masks.shape
+        T, H, W = tgt.shape
+        n = pair_src.numel()
+        dev = pred_masks.device
+        lib = _cabi.lib()
+        with torch.cuda.device(dev):
+            losses = torch.empty((2,), dtype=torch.float32, device=dev)
+            sums = torch.empty((n, 4), dtype=torch.float64, device=dev)
+            nbytes = lib.tf_mask_loss_workspace_bytes(n, H, W)
+            if nbytes < 0:
+                _cabi.check(-2, "tf_mask_loss_workspace_bytes")
+            ws = torch.empty((nbytes // 8,), dtype=torch.float64, device=dev)
+            rc = lib.tf_mask_loss_fwd_f32(pred_masks.data_ptr(), tgt.data_ptr(), pair_src.data_ptr(), pair_tgt.data_ptr(), sums.data_ptr(),
+                                          losses.data_ptr(), ws.data_ptr(), nbytes, n, B * Q, T, h, w, H, W, alpha, gamma, num_boxes,
+                                          _stream(dev))
+        _cabi.check(rc, "tf_mask_loss_fwd_f32")
+        ctx.save_for_backward(pred_masks, tgt, pair_tgt, row_pair, sums)   # the inputs and [n, 4] sums: the backward recomputes
+        ctx.scalars = (alpha, gamma, num_boxes)
+        return losses
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_losses):
+        pred_masks, tgt, pair_tgt, row_pair, sums = ctx.saved_tensors
+        alpha, gamma, num_boxes = ctx.scalars
+        if not ctx.needs_input_grad[0]:
+            return (None,) * 8
+        B, Q, h, w = pred_masks.shape
+        T, H, W = tgt.shape
+        G = g_losses.to(torch.float32).contiguous()
+        with torch.cuda.device(pred_masks.device):
+            grad = torch.empty_like(pred_masks)
+            rc = _cabi.lib().tf_mask_loss_bwd_f32(G.data_ptr(), pred_masks.data_ptr(), tgt.data_ptr(), pair_tgt.data_ptr(), row_pair.data_ptr(),
+                                                  sums.data_ptr(), grad.data_ptr(), pair_tgt.numel(), B * Q, T, h, w, H, W, alpha, gamma,
+                                                  num_boxes, _stream(pred_masks.device))
+        _cabi.check(rc, "tf_mask_loss_bwd_f32")
+        return (grad,) + (None,) * 7
+
+
+def mask_losses_applies(pred_masks, target_masks):
+    """What the mask-loss kernels take: fp32 contiguous pred_masks [B, Q, h, w] on the device and bool / uint8 target masks [T, H, W] on
+    the same device with H >= h and W >= w (the kernels upsample; they do not downsample)."""
+    return (pred_masks.is_cuda and pred_masks.dtype == torch.float32 and pred_masks.dim() == 4 and pred_masks.numel() > 0
+            and pred_masks.is_contiguous() and target_masks.dtype in (torch.bool, torch.uint8) and target_masks.device == pred_masks.device
+            and target_masks.dim() == 3 and target_masks.shape[1] >= pred_masks.shape[2] and target_masks.shape[2] >= pred_masks.shape[3])
+
+
+def mask_losses(pred_masks, target_masks, pair_src, pair_tgt, alpha, gamma, num_boxes, row_pair=None):
+    """The sigmoid focal and dice losses of the matched masks through tf_mask_loss_fwd_f32 / tf_mask_loss_bwd_f32 (include/tf_fused.h:
+    THE MASK LOSSES) -> [2] = (loss_mask, loss_dice), differentiable with respect to pred_masks.  pred_masks [B, Q, h, w] fp32 on the
+    device; target_masks bool / uint8 [T, H, W], the padded stack of all images' masks -- read as bytes, never converted or gathered;
+    pair_src int32 [n] (b * Q + q of every matched prediction), pair_tgt int32 [n] (its row of target_masks); row_pair int32 [B * Q]
+    (the pair of each row or -1; built here on the device when None -- the route uploads it with the pairs).  The bilinear upsampling to
+    H x W happens inside the kernels; only pred_masks, the index tensors and [n, 4] sums are kept for the backward.  Anything the kernels
+    do not take is an error here, not a fall-back (the caller decides the route: mask_losses_applies)."""
+    if not mask_losses_applies(pred_masks, target_masks):
+        raise ValueError("mask_losses: contiguous fp32 device pred_masks [B, Q, h, w] and bool / uint8 targets [T, H >= h, W >= w] expected")
+    n, rows = pair_src.numel(), pred_masks.shape[0] * pred_masks.shape[1]
+    for t, size in ((pair_src, n), (pair_tgt, n)) + (() if row_pair is None else ((row_pair, rows),)):
+        if t.dtype != torch.int32 or t.numel() != size or t.device != pred_masks.device or not t.is_contiguous():
+            raise ValueError("mask_losses: pair_src / pair_tgt int32 [n] and row_pair int32 [B Q] on the device expected")
+    tgt = target_masks.contiguous()
+    tgt = tgt.view(torch.uint8) if tgt.dtype == torch.bool else tgt
+    if row_pair is None:
+        row_pair = torch.full((rows,), -1, dtype=torch.int32, device=pred_masks.device)
+        if n:
+            row_pair[pair_src.long()] = torch.arange(n, dtype=torch.int32, device=pred_masks.device)
+    return _MaskLosses.apply(pred_masks, tgt, pair_src, pair_tgt, row_pair, float(alpha), float(gamma), float(num_boxes))

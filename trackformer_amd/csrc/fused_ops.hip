@@ -141,6 +141,7 @@ bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 
 
 #include "layernorm_bwd.h"
 #include "criterion.h"
+#include "mask_loss.h"
 
 namespace {
 

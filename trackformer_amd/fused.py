@@ -1710,5 +1710,6 @@ def layernorm_train(x, res, norm):
 # THE SET CRITERION AND THE MATCHING COST (opt-in; include/tf_fused.h; csrc/criterion.h).  The operators live in criterion_ops.py and
 # are re-exported here: every function DEFINED in this module whose name starts with set_ is a process-wide switch that returns its
 # previous value (tests/test_weight_coherence_cpu.py walks them), and set_criterion is an operator -- "set" as in set prediction --,
-# not a switch.  The switches of the two routes live with their callers: criterion.set_fused, matcher.set_fused_cost.
-from .criterion_ops import criterion_applies, match_cost, set_criterion   # noqa: E402,F401
+# not a switch.  The switches of the routes live with their callers: criterion.set_fused, criterion.set_fused_masks (THE MASK LOSSES;
+# csrc/mask_loss.h: mask_losses / mask_losses_applies), matcher.set_fused_cost.
+from .criterion_ops import criterion_applies, mask_losses, mask_losses_applies, match_cost, set_criterion   # noqa: E402,F401
