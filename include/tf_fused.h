@@ -306,6 +306,14 @@ int tf_linear_packed_f32(const float *x, const void *w_packed, const float *bias
  *                                tf_linear_pack_weight_f32(w^T [K, N] row-major, K = N, N = K, terms); dy is multiplied by s as it
  *                                is staged and the result by 1 / s: bit-identical to (1 / s) . tf_linear_packed_f32(s dy, wt_packed).
  *                                dy_scale2 may be NULL (no scaling).  N % 64 == 0, 16-byte aligned dy / wt_packed, dx below 3 GiB.
+ *   tf_linear_dgrad_splitk_packed_f32  the same product with the contraction over N cut into ksplit (1 .. 64) pieces, the stream GEMM's
+ *                                split-K: every piece's partial sum leaves its workgroup multiplied by 1 / s into workspace (ksplit M K
+ *                                floats), a second launch adds the pieces in the order 0, 1, ...; no accumulator walks the whole sum
+ *                                (the matrix cores do not add in round-to-nearest: a long chain collects a one-sided error).
+ *                                ksplit = 1: the bits of tf_linear_dgrad_packed_f32, workspace may be NULL.  ksplit > 1 also needs
+ *                                K % 4 == 0 and 16-byte aligned dx / workspace.  Checked in this order: NULL dy / wt_packed / dx, or a
+ *                                NULL workspace with ksplit > 1 -> TF_MSDA_ERR_NULL_POINTER; dimensions, ksplit, alignment (workspace
+ *                                included) -> TF_MSDA_ERR_BAD_DIMS.
  * Checked in this order, before any GPU work: NULL pointer -> TF_MSDA_ERR_NULL_POINTER, dimensions / alignment -> TF_MSDA_ERR_BAD_DIMS,
  * workspace too small or misaligned -> TF_MSDA_ERR_WORKSPACE.  The *_workspace_bytes functions return -1 for dimensions the entry
  * point rejects.
@@ -318,6 +326,59 @@ int tf_linear_wgrad_split_f32(const float *dy, const float *x, const float *dy_s
                               int64_t workspace_bytes, int64_t M, int K, int N, int terms, void *stream);
 int tf_linear_dgrad_packed_f32(const float *dy, const float *dy_scale2, const void *wt_packed, float *dx, int64_t M, int K, int N,
                                int terms, void *stream);
+int tf_linear_dgrad_splitk_packed_f32(const float *dy, const float *dy_scale2, const void *wt_packed, float *dx, float *workspace, int ksplit,
+                                      int64_t M, int K, int N, int terms, void *stream);
+
+/*
+ * THE BACKWARD OF A 3 x 3 CONVOLUTION  y = conv3x3(x, w), padding 1, stride s, no groups, no dilation  as split products
+ * (trackformer_amd/csrc/conv_bwd.h; reference: the autograd of the Bottleneck conv2 layers of models/backbone.py's ResNet-50, fp32).
+ * Every tensor is NHWC fp32 (the storage of a channels_last tensor): x [nimg, hin, win, cin], dy [nimg, hout, wout, cout] with
+ * hout = (hin - 1) / s + 1, wout = (win - 1) / s + 1; the weight is [cout, 3, 3, cin], tap-major (the storage of a channels_last OIHW
+ * weight).  With M = nimg hout wout output pixels m = (n, ho, wo):
+ *     dw[co, ky, kx, ci] = sum_m dy[m, co] x[n, ho s + ky - 1, wo s + kx - 1, ci]         (input pixels outside the image: exact zeros)
+ *     dx = conv3x3(dy, w_rot),  w_rot[ci, ky, kx, co] = w[co, 2 - ky, 2 - kx, ci]          (s = 1)
+ * These are the two products of THE BACKWARD OF A LINEAR on the unfolded matrix U[M, 9 cin] (tap-major columns, zeros at the borders),
+ * which is never materialised; scaling, the absence of atomics and the behaviour on non-finite operands are as stated there.
+ *
+ *   tf_conv3x3_wgrad_split_f32   s = 1 or 2.  dy is split as the activation (role 0, dy_scale2 = {s, 1 / s} from tf_linear_grad_stats_f32 of
+ *                                dy viewed as [M, cout]); x as the weight (role 1, x_scale2 = t[cin] | 1 / t[cin] from
+ *                                tf_linear_grad_stats_f32 of x viewed as [nimg hin win, cin]: one scale per input channel, shared by the
+ *                                nine taps).  The kernel is the one of tf_linear_wgrad_split_f32 (128 x 128 outputs per workgroup, slices of
+ *                                32 pixels) with the row address of x replaced: column k of the tile decodes once per thread into
+ *                                (tap, ci), a row m into (n, ho, wo) once per 8 rows; a shifted pixel that leaves the image contributes a
+ *                                zero and is never read.  Epilogue (fp16 scheme): 16 / (s t_ci).  The pixel loop is cut into the chunks of
+ *                                tf_linear_wgrad_split_f32 for (M, K = 9 cin, N = cout) -- the same rule, the same "wgrad_msplit" knob, the
+ *                                same second launch; tf_conv3x3_wgrad_workspace_bytes(...) = msplit cout 9 cin 4 bytes (0 for one chunk:
+ *                                workspace may be NULL).  Summation order per output: m ascending, per 16 pixels smallest term first; then
+ *                                the chunks in order.  The result equals tf_linear_wgrad_split_f32(dy, U, dy_scale2, x_scale2 repeated
+ *                                nine times) BIT FOR BIT, for both term schemes.
+ *                                cin % 4 == 0, cout % 4 == 0, 16-byte aligned dy / x / dw / x_scale2 / workspace, dy / x / dw below
+ *                                3 GiB each, M < 2^31, else TF_MSDA_ERR_BAD_DIMS.
+ *   tf_conv3x3_dgrad_packed_f32  stride 1 only (hout = hin = h, wout = win = w).  wrot_packed = tf_linear_pack_weight_f32(w_rot viewed as
+ *                                [cin, 9 cout], K = 9 cout, N = cin, terms).  This is tf_conv_packed_f32(ks = 3, stride = 1) with dy as
+ *                                the input and the same (workspace, ksplit), in the kernels' scaled-activation instantiation: dy is
+ *                                multiplied by s as it is staged, the result by 1 / s -- with ksplit = 1 bit-identical to
+ *                                (1 / s) . tf_conv_packed_f32(s dy, wrot_packed).  ksplit in 2 .. 64 cuts the contraction of 9 cout
+ *                                products into pieces as tf_conv_packed_f32 does (workspace: ksplit . nimg h w cin floats, 16-byte
+ *                                aligned; one fp32 accumulator then walks a piece, not the whole sum): every piece leaves its
+ *                                workgroup multiplied by 1 / s and the second pass adds them in the order 0, 1, ... -- the bits of
+ *                                (1 / s) . tf_conv_packed_f32(s dy, wrot_packed, ksplit) unless a partial sum is an fp32 subnormal.  BOTH
+ *                                forms of that entry point take the scaled instantiation with the same bits, so the choice is
+ *                                tf_conv_packed_f32's own: the HALO form unless tf_msda_set_option("conv_halo", 0) selects the plain
+ *                                stream form (the two differ in summation order; the identity above holds under either setting).
+ *                                dy_scale2 may be NULL (no scaling: tf_conv_packed_f32 itself).
+ *                                cout % 64 == 0, cin % 4 == 0, 16-byte aligned dy / wrot_packed / dx, dy and dx (+ 256 rows) below 3 GiB.
+ * Checked before any GPU work.  tf_conv3x3_wgrad_split_f32, in this order: NULL pointer -> TF_MSDA_ERR_NULL_POINTER, dimensions /
+ * alignment -> TF_MSDA_ERR_BAD_DIMS, workspace NULL, too small or misaligned -> TF_MSDA_ERR_WORKSPACE; tf_conv3x3_wgrad_workspace_bytes
+ * returns -1 for dimensions the entry point rejects.  tf_conv3x3_dgrad_packed_f32, in this order (as tf_conv_packed_f32, whose
+ * workspace has no size argument): NULL dy / wrot_packed / dx, or a NULL workspace with ksplit > 1 -> TF_MSDA_ERR_NULL_POINTER;
+ * dimensions, ksplit outside 1 .. 64, alignment (a misaligned workspace included) -> TF_MSDA_ERR_BAD_DIMS.
+ */
+int64_t tf_conv3x3_wgrad_workspace_bytes(int nimg, int hin, int win, int cin, int cout, int stride);
+int tf_conv3x3_wgrad_split_f32(const float *dy, const float *x, const float *dy_scale2, const float *x_scale2, float *dw, void *workspace,
+                               int64_t workspace_bytes, int nimg, int hin, int win, int cin, int cout, int stride, int terms, void *stream);
+int tf_conv3x3_dgrad_packed_f32(const float *dy, const float *dy_scale2, const void *wrot_packed, float *dx, float *workspace, int ksplit,
+                                int nimg, int h, int w, int cin, int cout, int terms, void *stream);
 
 /*
  * THE BACKWARD OF THE RESIDUAL LAYERNORM  out = LayerNorm(x + res) gamma + beta  (trackformer_amd/csrc/layernorm_bwd.h; reference: the

@@ -66,6 +66,10 @@ EXPORTED_SYMBOLS = (
     "tf_linear_wgrad_workspace_bytes",
     "tf_linear_wgrad_split_f32",
     "tf_linear_dgrad_packed_f32",
+    "tf_linear_dgrad_splitk_packed_f32",
+    "tf_conv3x3_wgrad_workspace_bytes",
+    "tf_conv3x3_wgrad_split_f32",
+    "tf_conv3x3_dgrad_packed_f32",
     "tf_add_layernorm_train_f32",
     "tf_add_layernorm_bwd_workspace_bytes",
     "tf_add_layernorm_bwd_f32",
@@ -217,6 +221,14 @@ def lib():
     L.tf_linear_wgrad_split_f32.argtypes = [vp, vp, vp, vp, vp, vp, i64, i64, ci, ci, ci, vp]
     L.tf_linear_dgrad_packed_f32.restype = ci
     L.tf_linear_dgrad_packed_f32.argtypes = [vp, vp, vp, vp, i64, ci, ci, ci, vp]
+    L.tf_linear_dgrad_splitk_packed_f32.restype = ci
+    L.tf_linear_dgrad_splitk_packed_f32.argtypes = [vp, vp, vp, vp, vp, ci, i64, ci, ci, ci, vp]
+    L.tf_conv3x3_wgrad_workspace_bytes.restype = i64
+    L.tf_conv3x3_wgrad_workspace_bytes.argtypes = [ci] * 6
+    L.tf_conv3x3_wgrad_split_f32.restype = ci
+    L.tf_conv3x3_wgrad_split_f32.argtypes = [vp, vp, vp, vp, vp, vp, i64] + [ci] * 7 + [vp]
+    L.tf_conv3x3_dgrad_packed_f32.restype = ci
+    L.tf_conv3x3_dgrad_packed_f32.argtypes = [vp, vp, vp, vp, vp] + [ci] * 7 + [vp]
     L.tf_add_layernorm_train_f32.restype = ci
     L.tf_add_layernorm_train_f32.argtypes = [vp, vp, vp, vp, vp, vp, i64, ci, ctypes.c_float, vp]
     L.tf_add_layernorm_bwd_workspace_bytes.restype = i64

@@ -227,6 +227,43 @@ def set_train_fold(on: bool) -> bool:
     return fused._switched(prev, _train_fold)
 
 
+# OPT-IN (TF_SPLIT_CONV_TRAIN=1 / set_split_conv_training(True)): the convolutions of the TRAINABLE bottlenecks (mode 2 above: layer2-4)
+# through fused.conv_train -- the inference route's forward kernels and the library's own input- and weight-gradient kernels
+# (include/tf_fused.h: THE BACKWARD OF A 3 x 3 CONVOLUTION; the 1 x 1 stride-1 layers through fused.linear_train's) instead of
+# F.conv2d's MIOpen / CK forward and backward; the weight fold and _BiasAct stay what they are.  NOT covered: the strided 1 x 1
+# projections of the identity branch, the input gradient of the three stride-2 3 x 3 layers (torch inside the backward, counted), the
+# stem, input_proj.  OFF by default: whether it is faster inside a training step is a measurement (tools/bench_conv_backward.py,
+# profiles/conv_backward_bench.json), not a promise.
+_split_conv_train = None    # None: follow TF_SPLIT_CONV_TRAIN (unset: off)
+
+
+def split_conv_training_enabled():
+    if _split_conv_train is not None:
+        return _split_conv_train
+    return _os.environ.get("TF_SPLIT_CONV_TRAIN", "0") not in ("", "0")
+
+
+def set_split_conv_training(flag):
+    """Switch the split-product training path of the trainable bottlenecks' convolutions on or off (process-wide; None: follow
+    TF_SPLIT_CONV_TRAIN again); returns the previous setting."""
+    global _split_conv_train
+    prev = split_conv_training_enabled()
+    _split_conv_train = None if flag is None else bool(flag)
+    return fused._switched(prev, split_conv_training_enabled())
+
+
+def _conv_train(x, conv, w_f):
+    """fused.conv_train for the shapes it covers (w_f: the folded OIHW weight, an autograd tensor), else None."""
+    if conv.groups != 1 or conv.dilation != (1, 1) or not CHANNELS_LAST:
+        return None
+    cout, cin = conv.out_channels, conv.in_channels
+    if conv.kernel_size == (3, 3) and conv.padding == (1, 1) and conv.stride in ((1, 1), (2, 2)):
+        return fused.conv_train(x, w_f.permute(0, 2, 3, 1).reshape(cout, 9 * cin), conv.stride[0])
+    if conv.kernel_size == (1, 1) and conv.padding == (0, 0) and conv.stride == (1, 1):
+        return fused.conv_train(x, w_f.reshape(cout, cin), 1)
+    return None
+
+
 def _frozen(module: nn.Module) -> bool:
     f = module.__dict__.get("_tf_frozen")
     if f is None or f[0] != _frozen_epoch[0]:
@@ -288,7 +325,13 @@ def _conv_bn(x, conv: nn.Conv2d, bn: nn.Module, cache: _FoldCache, relu: bool, f
     the BN scale folded into its weights, then ONE fused pass for shift / residual / ReLU."""
     if fold == 2 and isinstance(bn, FrozenBatchNorm2d) and x.is_cuda:
         scale, shift = bn.scale_shift()
-        y = F.conv2d(x, conv.weight * scale.reshape(-1, 1, 1, 1), None, conv.stride, conv.padding, conv.dilation, conv.groups)
+        if split_conv_training_enabled():
+            w_f = conv.weight * scale.reshape(-1, 1, 1, 1)
+            y = _conv_train(x, conv, w_f)
+            if y is None:
+                y = F.conv2d(x, w_f, None, conv.stride, conv.padding, conv.dilation, conv.groups)
+        else:
+            y = F.conv2d(x, conv.weight * scale.reshape(-1, 1, 1, 1), None, conv.stride, conv.padding, conv.dilation, conv.groups)
         if y.requires_grad:
             return _BiasAct.apply(y, shift, residual, relu)
         fold = 0   # (nothing here is differentiated and the block is not frozen either: cannot happen for a trainable weight)

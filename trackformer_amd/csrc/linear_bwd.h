@@ -177,10 +177,31 @@ grad_stats_final_kernel(const unsigned *__restrict__ pmax, const float *__restri
 // Summation order per output: m ascending, per 16 rows smallest term first; then the chunks in order.
 constexpr int kWgTile = 128, kWgSlice = 32, kWgStride = kWgSlice + 8;
 
-template <int SP>
-__global__ void __launch_bounds__(256)
-wgrad_kernel(const float *__restrict__ dy, const float *__restrict__ x, const float *__restrict__ dy_scale2,
-             const float *__restrict__ x_scale2, float *__restrict__ out, int M, int N, int K, int ktiles, int spc)
+// The x operand is reached through a ROW MAP (the tile, the staging, the MFMAs and the epilogue are shared with the weight gradient of
+// the 3 x 3 convolution, conv_bwd.h, whose x[m, k] is a shifted input pixel): init(k, ok) takes the thread's column once, load8(m0, M,
+// dst) fetches rows m0 .. m0 + 7 of it (exact zeros where there is no such element), scale(k) / inv_scale(k) are t_k and 1 / t_k.
+struct WgradRowsLinear {   // x[M, K] row-major
+    const float *x, *x_scale2;
+    int K;
+    const float *bp;
+    bool bok;
+    __device__ __forceinline__ void init(int k, bool ok)
+    {
+        bok = ok;
+        bp = x + (ok ? k : 0);
+    }
+    __device__ __forceinline__ void load8(int m0, int M, float (&dst)[8]) const
+    {
+#pragma unroll
+        for (int r = 0; r < 8; ++r) dst[r] = (m0 + r < M && bok) ? bp[(size_t)(m0 + r) * K] : 0.f;
+    }
+    __device__ __forceinline__ float scale(int k) const { return x_scale2[k]; }
+    __device__ __forceinline__ float inv_scale(int k) const { return x_scale2[K + k]; }
+};
+
+template <int SP, class XROWS>
+__device__ __forceinline__ void wgrad_tile(const float *__restrict__ dy, const float *__restrict__ dy_scale2, float *__restrict__ out,
+                                           int M, int N, int K, int ktiles, int spc, XROWS xrows)
 {
     constexpr int NA = Split<SP>::NA, NB = Split<SP>::NB;
     __shared__ __attribute__((aligned(16))) unsigned short sA[NA][kWgTile * kWgStride];   // dy^T pieces: [n][m]
@@ -210,20 +231,19 @@ wgrad_kernel(const float *__restrict__ dy, const float *__restrict__ x, const fl
     // ---- staging: thread -> column c of the tile, row groups g0 and g0 + 1 (8 rows each) of the slice
     const int c = tid & 127, g0 = (tid >> 7) * 2;
     const bool aok = n0 + c < N, bok = k0 + c < K;
-    const float *ap = dy + (aok ? n0 + c : 0), *bp = x + (bok ? k0 + c : 0);
+    const float *ap = dy + (aok ? n0 + c : 0);
+    xrows.init(k0 + c, bok);
     float sb = 1.f;   // the scale of this thread's column of x
-    if constexpr (Split<SP>::F16) sb = bok ? x_scale2[k0 + c] : 1.f;
+    if constexpr (Split<SP>::F16) sb = bok ? xrows.scale(k0 + c) : 1.f;
     float ra[2][8], rb[2][8];
     auto load = [&](int s) {
 #pragma unroll
-        for (int h = 0; h < 2; ++h)
+        for (int h = 0; h < 2; ++h) {
+            const int m0 = s * kWgSlice + (g0 + h) * 8;
 #pragma unroll
-            for (int r = 0; r < 8; ++r) {
-                const int m = s * kWgSlice + (g0 + h) * 8 + r;
-                const bool mok = m < M;
-                ra[h][r] = (mok && aok) ? ap[(size_t)m * N] : 0.f;
-                rb[h][r] = (mok && bok) ? bp[(size_t)m * K] : 0.f;
-            }
+            for (int r = 0; r < 8; ++r) ra[h][r] = (m0 + r < M && aok) ? ap[(size_t)(m0 + r) * N] : 0.f;
+            xrows.load8(m0, M, rb[h]);
+        }
     };
     auto store = [&]() {
 #pragma unroll
@@ -275,7 +295,7 @@ wgrad_kernel(const float *__restrict__ dy, const float *__restrict__ x, const fl
         const int k = k0 + (wc * 2 + j) * 32 + (lane & 31);
         const bool kok = k < K;
         float fb = 1.f;
-        if constexpr (Split<SP>::F16) fb = kok ? 4.f * x_scale2[K + k] : 1.f;
+        if constexpr (Split<SP>::F16) fb = kok ? 4.f * xrows.inv_scale(k) : 1.f;
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int nrow0 = n0 + (wr * 2 + i) * 32 + 4 * (lane >> 5);
@@ -288,6 +308,14 @@ wgrad_kernel(const float *__restrict__ dy, const float *__restrict__ x, const fl
             }
         }
     }
+}
+
+template <int SP>
+__global__ void __launch_bounds__(256)
+wgrad_kernel(const float *__restrict__ dy, const float *__restrict__ x, const float *__restrict__ dy_scale2,
+             const float *__restrict__ x_scale2, float *__restrict__ out, int M, int N, int K, int ktiles, int spc)
+{
+    wgrad_tile<SP>(dy, dy_scale2, out, M, N, K, ktiles, spc, WgradRowsLinear{x, x_scale2, K, nullptr, false});
 }
 
 struct WgradPlan {
@@ -401,6 +429,24 @@ extern "C" int tf_linear_dgrad_packed_f32(const float *dy, const float *dy_scale
     if ((long long)(M + 256) * K * 4 >= 0xC0000000LL) return TF_MSDA_ERR_BAD_DIMS;
     // (`bias` carries scale2: the XSC form of stream_gemm_kernel)
     StreamCall c{dy, static_cast<const u32x4 *>(wt_packed), dy_scale2, nullptr, dx, (int)M, N, K, 0, false, StreamConv{}, nullptr, 1};
+    const bool scaled = dy_scale2 != nullptr;
+    return sp == 3 ? dgrad_dispatch<3>(c, static_cast<hipStream_t>(stream), scaled) : dgrad_dispatch<16>(c, static_cast<hipStream_t>(stream), scaled);
+}
+
+// the same product with the contraction over N cut into `ksplit` pieces (the stream GEMM's split-K: partial sums to `workspace`, each
+// multiplied by 1 / s, a second launch adds them in the order 0, 1, ...): no accumulator walks the whole sum.  ksplit = 1: the bits of
+// tf_linear_dgrad_packed_f32
+extern "C" int tf_linear_dgrad_splitk_packed_f32(const float *dy, const float *dy_scale2, const void *wt_packed, float *dx, float *workspace,
+                                                 int ksplit, int64_t M, int K, int N, int terms, void *stream)
+{
+    if (!dy || !wt_packed || !dx) return TF_MSDA_ERR_NULL_POINTER;
+    if (ksplit > 1 && !workspace) return TF_MSDA_ERR_NULL_POINTER;
+    const int sp = split_scheme(terms);
+    if (M <= 0 || K <= 0 || N <= 0 || (N % 64) != 0 || M > 0x7fffffffLL || sp == 0 || ksplit < 1 || ksplit > 64) return TF_MSDA_ERR_BAD_DIMS;
+    if (!aligned16(dy) || !aligned16(wt_packed)) return TF_MSDA_ERR_BAD_DIMS;
+    if (ksplit > 1 && ((K & 3) || !aligned16(dx) || !aligned16(workspace))) return TF_MSDA_ERR_BAD_DIMS;   // (the second pass moves float4)
+    if ((long long)(M + 256) * K * 4 >= 0xC0000000LL) return TF_MSDA_ERR_BAD_DIMS;
+    StreamCall c{dy, static_cast<const u32x4 *>(wt_packed), dy_scale2, nullptr, dx, (int)M, N, K, 0, false, StreamConv{}, workspace, ksplit};
     const bool scaled = dy_scale2 != nullptr;
     return sp == 3 ? dgrad_dispatch<3>(c, static_cast<hipStream_t>(stream), scaled) : dgrad_dispatch<16>(c, static_cast<hipStream_t>(stream), scaled);
 }

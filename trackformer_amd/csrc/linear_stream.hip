@@ -680,7 +680,9 @@ struct HaloMerge {
     float eps;
 };
 
-template <int SP, int TI, int TJ, int WC, bool MRG = false>
+// XSC (the input gradient of a 3 x 3 convolution, tf_conv3x3_dgrad_packed_f32 in conv_bwd.h; off in every other instantiation): as in
+// stream_gemm_kernel -- `bias` carries scale2 = {s, 1 / s}, the halo is multiplied by s as it is staged, the result by 1 / s.
+template <int SP, int TI, int TJ, int WC, bool MRG = false, bool XSC = false>
 __global__ void __launch_bounds__(kThreads, (TI * TJ <= 2 ? 2 : 1))
 conv3x3_halo_kernel(const float *__restrict__ X, const u32x4 *__restrict__ Wp, const float *__restrict__ bias, const float *R, float *Y,
                     int N, int nblocks, int npatches, int tiles_x, int tiles_y, int relu, int cslices, const StreamConv cv,
@@ -707,6 +709,11 @@ conv3x3_halo_kernel(const float *__restrict__ X, const u32x4 *__restrict__ Wp, c
     const int cend = cslices > 0 ? min(nsl, cbeg + cslices) : nsl;
     const long long Mtot = (long long)cv.nimg * H * W;
     if (cslices > 0) Y += (size_t)blockIdx.y * Mtot * N;
+    float xsc = 1.f, xinv = 1.f;
+    if constexpr (XSC) {
+        xsc = bias[0];
+        xinv = bias[1];
+    }
 
     f32x16 acc[TI][TJ];
 #pragma unroll
@@ -796,7 +803,8 @@ conv3x3_halo_kernel(const float *__restrict__ X, const u32x4 *__restrict__ Wp, c
                 v += src.f[it];
             }
             u32x2 pc[NA];
-            split4<SP>(v, pc);
+            if constexpr (XSC) split4<SP>(v * xsc, pc);
+            else split4<SP>(v, pc);
 #pragma unroll
             for (int p = 0; p < NA; ++p) *reinterpret_cast<u32x2 *>(&sH[buf][p][lds_o[it]]) = pc[p];
         }
@@ -918,7 +926,7 @@ conv3x3_halo_kernel(const float *__restrict__ X, const u32x4 *__restrict__ Wp, c
     for (int j = 0; j < TJ; ++j) {
         const int col = n0 + (wc * TJ + j) * 32 + (lane & 31);
         const bool colok = col < N;
-        const float b = (bias && colok) ? bias[col] : 0.f;
+        const float b = (!XSC && bias && colok) ? bias[col] : 0.f;
         float rsc = 1.f;   // fp16 scheme: the output channel's power of two (behind the fragments of the packed weight)
         if constexpr (Split<SP>::F16) rsc = reinterpret_cast<const float *>(Wp + (size_t)((N + kBN - 1) / kBN * (kBN / 32)) * KQ * NB * 64)[colok ? col : 0];
 #pragma unroll
@@ -940,6 +948,7 @@ conv3x3_halo_kernel(const float *__restrict__ X, const u32x4 *__restrict__ Wp, c
                 float v = Split<SP>::F16 ? __builtin_fmaf(acc[i][j][e], rsc, b) : acc[i][j][e] + b;
                 if (R != nullptr) v += rv[e];
                 if (relu) v = v < 0.f ? 0.f : v;
+                if constexpr (XSC) v *= xinv;
                 __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), yrs, off[e], 0, tfm::kStoreAux);
             }
         }
@@ -986,10 +995,10 @@ int launch_stream(const StreamCall &c, hipStream_t s)
     const bool partial = gz > 1;
     float *out = partial ? c.workspace : c.y;
     hipLaunchKernelGGL((stream_gemm_kernel<SP, TI, TJ, WC, CONV, XSC>), dim3((unsigned)gx, (unsigned)gz), dim3(kThreads), 0, s, c.x, c.wp,
-                       partial ? nullptr : c.bias, partial ? nullptr : c.res, out, c.M, c.K, c.N, mblocks, nblocks, partial ? 0 : c.relu,
-                       kslices, c.cv);
+                       (partial && !XSC) ? nullptr : c.bias, partial ? nullptr : c.res, out, c.M, c.K, c.N, mblocks, nblocks, partial ? 0 : c.relu,
+                       kslices, c.cv);   // (XSC: `bias` is scale2 -- every partial sum is staged with s and leaves with 1 / s)
     if (hipGetLastError() != hipSuccess) return TF_MSDA_ERR_LAUNCH;
-    return partial ? launch_splitk_reduce(c.workspace, c.bias, c.res, c.y, (long long)c.M * c.N, c.N, gz, c.relu, s) : TF_MSDA_OK;
+    return partial ? launch_splitk_reduce(c.workspace, XSC ? nullptr : c.bias, c.res, c.y, (long long)c.M * c.N, c.N, gz, c.relu, s) : TF_MSDA_OK;
 }
 
 // Block shape per call.  Columns: N <= 64 -> 64-column blocks (2 x 2 waves), N <= 128 -> 128 (4 waves side by side, one column
@@ -997,39 +1006,39 @@ int launch_stream(const StreamCall &c, hipStream_t s)
 // 256-column blocks): two row tiles win at K = 256 (59.3 / 67.3 / 84.2 us for TI = 2 / 3 / 4 at N = 1024: a block's eight K-slices
 // are too short a loop to hide its own memory latency and the co-resident blocks have to), three at K = 1024 (55.6 / 50.5 / 58.0).
 // The narrow shapes take 128-row blocks while that leaves at least ~2 blocks per CU, else 64.
-template <int SP, bool CONV>
+template <int SP, bool CONV, bool XSC = false>
 int stream_dispatch(const StreamCall &c, hipStream_t s)
 {
     const int f = tfm::dense_knob(tfm::kKnobLinearStreamTi);
     const long long pieces = c.ksplit > 1 ? c.ksplit : 1;
     if (c.N <= 64) {
         const bool big = f ? f >= 2 : (long long)((c.M + 127) / 128) * pieces >= 2LL * tfm::num_cus();
-        return big ? launch_stream<SP, 2, 1, 2, CONV>(c, s) : launch_stream<SP, 1, 1, 2, CONV>(c, s);
+        return big ? launch_stream<SP, 2, 1, 2, CONV, XSC>(c, s) : launch_stream<SP, 1, 1, 2, CONV, XSC>(c, s);
     }
     if (c.N <= 128) {
         // (round 5, measured and removed: 128 x 128 blocks as 2 x 2 waves of 64 x 64 -- half the LDS re-reads of the activations per
         // MFMA, twice the weight fragments per wave: 150.6 us against 146.9 at 131 072 rows, profiles/r05_conv3_tiles_2x2_waves.txt)
         const bool big = f ? f >= 4 : (long long)((c.M + 127) / 128) * pieces >= 2LL * tfm::num_cus();
-        return big ? launch_stream<SP, 4, 1, 4, CONV>(c, s) : launch_stream<SP, 2, 1, 4, CONV>(c, s);
+        return big ? launch_stream<SP, 4, 1, 4, CONV, XSC>(c, s) : launch_stream<SP, 2, 1, 4, CONV, XSC>(c, s);
     }
     if constexpr (CONV) {   // (three row tiles of the convolution form do not fit the register file with three pieces)
         const bool big = f ? f >= 4 : (long long)((c.M + 127) / 128) * ((c.N + 255) / 256) * pieces >= 2LL * tfm::num_cus();
-        return big ? launch_stream<SP, 4, 2, 4, CONV>(c, s) : launch_stream<SP, 2, 2, 4, CONV>(c, s);
+        return big ? launch_stream<SP, 4, 2, 4, CONV, XSC>(c, s) : launch_stream<SP, 2, 2, 4, CONV, XSC>(c, s);
     } else {
         // (fp16 pieces: three row tiles at every K -- 22 223 rows: 256 -> 1024 48.8 vs 51.3 us, 1024 -> 256 43.2 vs 50.5, 256 -> 256
         // 18.2 vs 18.6; profiles/r04_f16_harness.txt)
         switch (f ? f : (c.K >= 512 || SP == 16 ? 3 : 2)) {
         case 1:
-        case 2: return launch_stream<SP, 2, 2, 4, CONV>(c, s);
-        case 4: return launch_stream<SP, 4, 2, 4, CONV>(c, s);
-        default: return launch_stream<SP, 3, 2, 4, CONV>(c, s);
+        case 2: return launch_stream<SP, 2, 2, 4, CONV, XSC>(c, s);
+        case 4: return launch_stream<SP, 4, 2, 4, CONV, XSC>(c, s);
+        default: return launch_stream<SP, 3, 2, 4, CONV, XSC>(c, s);
         }
     }
 }
 
 // ---- the halo form: block shape per call (as stream_dispatch: 64 / 128 / 256 columns; 64-pixel patches, 128 where that still leaves
 // about two blocks per CU)
-template <int SP, int TI, int TJ, int WC, bool MRG = false>
+template <int SP, int TI, int TJ, int WC, bool MRG = false, bool XSC = false>
 int launch_halo(const StreamCall &c, hipStream_t s, const HaloMerge mg = HaloMerge{})
 {
     constexpr int BM = (4 / WC) * TI * 32, BN = WC * TJ * 32, PH = BM / 8;
@@ -1047,14 +1056,14 @@ int launch_halo(const StreamCall &c, hipStream_t s, const HaloMerge mg = HaloMer
     if (gx > 0x7fffffffLL || gz > 65535 || npatches > 0x7fffffffLL) return TF_MSDA_ERR_BAD_DIMS;
     const bool partial = gz > 1;
     float *out = partial ? c.workspace : c.y;
-    hipLaunchKernelGGL((conv3x3_halo_kernel<SP, TI, TJ, WC, MRG>), dim3((unsigned)gx, (unsigned)gz), dim3(kThreads), 0, s, c.x, c.wp,
-                       partial ? nullptr : c.bias, partial ? nullptr : c.res, out, c.N, nblocks, (int)npatches, tiles_x, tiles_y,
-                       partial ? 0 : c.relu, cslices, c.cv, mg);
+    hipLaunchKernelGGL((conv3x3_halo_kernel<SP, TI, TJ, WC, MRG, XSC>), dim3((unsigned)gx, (unsigned)gz), dim3(kThreads), 0, s, c.x, c.wp,
+                       (partial && !XSC) ? nullptr : c.bias, partial ? nullptr : c.res, out, c.N, nblocks, (int)npatches, tiles_x, tiles_y,
+                       partial ? 0 : c.relu, cslices, c.cv, mg);   // (XSC: as launch_stream)
     if (hipGetLastError() != hipSuccess) return TF_MSDA_ERR_LAUNCH;
-    return partial ? launch_splitk_reduce(c.workspace, c.bias, c.res, c.y, (long long)c.M * c.N, c.N, gz, c.relu, s) : TF_MSDA_OK;
+    return partial ? launch_splitk_reduce(c.workspace, XSC ? nullptr : c.bias, c.res, c.y, (long long)c.M * c.N, c.N, gz, c.relu, s) : TF_MSDA_OK;
 }
 
-template <int SP>
+template <int SP, bool XSC = false>
 int halo_dispatch(const StreamCall &c, hipStream_t s)
 {
     const int f = tfm::dense_knob(tfm::kKnobLinearStreamTi);
@@ -1065,10 +1074,10 @@ int halo_dispatch(const StreamCall &c, hipStream_t s)
     // 128-row blocks whatever the launch size: at Cin <= 64 a block's life is one or two slices -- cold halo, nine taps of weight
     // fragments from L2, epilogue -- and two resident blocks per CU overlap that better than one of twice the rows (MI355X, 128
     // queries: 32 -> 16 at 200 x 334 902 vs 1 101 us, 64 -> 32 at 100 x 167 402 vs 515; tools/experiments/mask_head_convs.py)
-    if (c.N <= 32) return (f >= 2) ? launch_halo<SP, 2, 1, 1>(c, s) : launch_halo<SP, 1, 1, 1>(c, s);
-    if (c.N <= 64) return (f ? f >= 2 : big) ? launch_halo<SP, 2, 1, 2>(c, s) : launch_halo<SP, 1, 1, 2>(c, s);
-    if (c.N <= 128) return (f ? f >= 4 : big) ? launch_halo<SP, 4, 1, 4>(c, s) : launch_halo<SP, 2, 1, 4>(c, s);
-    return launch_halo<SP, 2, 2, 4>(c, s);
+    if (c.N <= 32) return (f >= 2) ? launch_halo<SP, 2, 1, 1, false, XSC>(c, s) : launch_halo<SP, 1, 1, 1, false, XSC>(c, s);
+    if (c.N <= 64) return (f ? f >= 2 : big) ? launch_halo<SP, 2, 1, 2, false, XSC>(c, s) : launch_halo<SP, 1, 1, 2, false, XSC>(c, s);
+    if (c.N <= 128) return (f ? f >= 4 : big) ? launch_halo<SP, 4, 1, 4, false, XSC>(c, s) : launch_halo<SP, 2, 1, 4, false, XSC>(c, s);
+    return launch_halo<SP, 2, 2, 4, false, XSC>(c, s);
 }
 
 // the merged form (MRG): the mask head's shapes only -- one column tile of 32 (lay4 / lay5), 64 (lay3) or 128 channels
@@ -1235,3 +1244,5 @@ extern "C" int tf_conv_packed_f32(const float *x, const void *w_packed, const fl
 
 // the backward of a linear (statistics, weight gradient, input gradient): kernels and entry points
 #include "linear_bwd.h"
+// the backward of a 3 x 3 convolution: the same two products through the convolution's index map
+#include "conv_bwd.h"

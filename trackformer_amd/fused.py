@@ -1554,7 +1554,13 @@ class _LinearTrain(torch.autograd.Function):
                 packed_t = _packed_weight_t(weight, terms) if own and N % 64 == 0 and (M + 256) * K * 4 < 0xC0000000 else None
                 if packed_t is not None:
                     dx = torch.empty((M, K), dtype=torch.float32, device=dy2.device)
-                    rc = L.tf_linear_dgrad_packed_f32(dy2.data_ptr(), s_dy.data_ptr(), packed_t.data_ptr(), dx.data_ptr(), M, K, N, terms, stream)
+                    ks = getattr(ctx, "dgrad_ksplit", 1)   # (_Conv1x1Train: the contraction over N cut into pieces; the linears: one)
+                    if ks > 1:
+                        wsx = torch.empty((ks, M * K), dtype=torch.float32, device=dy2.device)
+                        rc = L.tf_linear_dgrad_splitk_packed_f32(dy2.data_ptr(), s_dy.data_ptr(), packed_t.data_ptr(), dx.data_ptr(),
+                                                                 wsx.data_ptr(), ks, M, K, N, terms, stream)
+                    else:
+                        rc = L.tf_linear_dgrad_packed_f32(dy2.data_ptr(), s_dy.data_ptr(), packed_t.data_ptr(), dx.data_ptr(), M, K, N, terms, stream)
                     _cabi.check(rc, "tf_linear_dgrad_packed_f32")
                     _train_counts["dgrad_own"] += 1
                 else:
@@ -1703,6 +1709,205 @@ def layernorm_train(x, res, norm):
         return None
     _layernorm_train_counts["own"] += 1
     return _LayerNormTrain.apply(x, res, norm.weight, norm.bias, norm.eps)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# THE TRAINING PATH OF THE BACKBONE'S CONVOLUTIONS (opt-in; include/tf_fused.h: THE BACKWARD OF A 3 x 3 CONVOLUTION; csrc/conv_bwd.h).
+# The switch lives with its caller (backbone.set_split_conv_training / TF_SPLIT_CONV_TRAIN=1: the trainable bottlenecks' conv + FrozenBN
+# pairs); conv_train below is the operator.  3 x 3, padding 1, stride 1 or 2: the forward is conv3x3() (bit-identical to the inference
+# route), the backward the library's statistics, input-gradient (stride 1) and weight-gradient kernels.  1 x 1, stride 1: _LinearTrain on
+# the pixel matrix of the channels_last activation.  No float atomics: bit-identical from call to call.  NOT covered: the strided 1 x 1
+# projections, the input gradient of a stride-2 3 x 3 (torch, counted), the stem, input_proj, the mask head, GroupNorm.
+_conv_train_counts = {"fwd_own": 0, "fwd_torch": 0, "dgrad_own": 0, "dgrad_torch": 0, "wgrad_own": 0, "wgrad_torch": 0}
+
+
+def conv_train_counts(reset=False):
+    """How conv_train's calls went: forwards it ran (fwd_own) or declined on device tensors (fwd_torch: the caller's F.conv2d), and
+    the input / weight gradients of its 3 x 3 calls by the library's own kernels or by torch.  (The gradients of the 1 x 1 calls are
+    linear_train's: train_route_counts().)"""
+    out = dict(_conv_train_counts)
+    if reset:
+        for k in _conv_train_counts:
+            _conv_train_counts[k] = 0
+    return out
+
+
+def _packed_weight_rot(w_taps, terms):
+    """Fragment-order image of w_rot[ci, ky, kx, co] = w[co, 2 - ky, 2 - kx, ci] as [Cin, 9 Cout] (the `weight` of the input gradient
+    dx = conv3x3(dy, w_rot)), cached on the tap-major weight under its source_key() like _packed_weight_t; None when it cannot be
+    built (shape; stream capture without a cached image).  The cache serves a weight tensor that persists; backbone._conv_bn hands
+    conv_train a new image of the folded weight every step, so there the image is packed once per call, and a training step captured
+    into a HIP graph finds none: its 3 x 3 input gradients are torch's (counted in conv_train_counts)."""
+    cache = getattr(w_taps, "_tf_packed_rot", None)
+    key = source_key(w_taps)
+    if cache is None or cache[0] != key:
+        cache = (key, {})
+        w_taps._tf_packed_rot = cache
+    capturing = torch.cuda.is_current_stream_capturing()
+    hit = cache[1].get(terms)
+    if hit is None:
+        if capturing:
+            return None   # never build a cached buffer inside a graph's memory pool
+        cout, cin = w_taps.shape[0], w_taps.shape[1] // 9
+        nbytes = _cabi.lib().tf_linear_packed_bytes(9 * cout, cin, terms)
+        if nbytes <= 0:
+            return None
+        with torch.cuda.device(w_taps.device):
+            wr = w_taps.detach().view(cout, 3, 3, cin).flip(1, 2).permute(3, 1, 2, 0).contiguous()
+            buf = torch.empty(nbytes, dtype=torch.uint8, device=w_taps.device)
+            rc = _cabi.lib().tf_linear_pack_weight_f32(wr.data_ptr(), buf.data_ptr(), 9 * cout, cin, terms, _stream(w_taps.device))
+        _cabi.check(rc, "tf_linear_pack_weight_f32")
+        hit = (buf, torch.cuda.current_stream(w_taps.device))
+        cache[1][terms] = hit
+    elif not capturing and hit[1] != torch.cuda.current_stream(w_taps.device):
+        torch.cuda.current_stream(w_taps.device).wait_stream(hit[1])
+    return hit[0]
+
+
+def _own_tensor(v):
+    """A tensor object of its own over the storage of v (a view made inside a Function's forward): what the Function returns is then
+    no view to autograd, and the caller may go on in place (backbone._BiasAct) as it does on F.conv2d's output."""
+    return torch.empty(0, dtype=v.dtype, device=v.device).set_(v.untyped_storage(), v.storage_offset(), v.size(), v.stride())
+
+
+class _Conv1x1Train(torch.autograd.Function):
+    """_LinearTrain on the [N H W, Cin] view of a channels_last activation: conv1x1_as_gemm with linear_train as its linear_fn (no bias,
+    residual or ReLU).  `bias` is always None: it keeps the argument positions _LinearTrain.backward reads.  Few pixels under a long
+    contraction are cut into pieces by the inference route's rule (conv1x1_wants_split_k / _conv_ksplit), in the forward (the
+    convolution kernel with its K loop cut, as backbone._conv_bn runs it in inference) and in the input gradient
+    (tf_linear_dgrad_splitk_packed_f32): more workgroups, and no matrix-core accumulator over the whole sum."""
+
+    @staticmethod
+    def forward(ctx, x, w2d, bias):
+        n, cin, h, wd = x.shape
+        cout, M = w2d.shape[0], n * h * wd
+        x2 = x.permute(0, 2, 3, 1).reshape(M, cin)   # a view: NHWC storage
+        y = None
+        if cin % 4 == 0 and conv1x1_wants_split_k(M, cin, cout):
+            with one_stream():
+                y = conv3x3(x, w2d, None, False, 1)
+        if y is not None:
+            ctx.relu = False
+            ctx.terms = 6 if (_split_terms == 16 and _routed(w2d)) else _split_terms
+            ctx.save_for_backward(x2, w2d, None)
+        else:
+            y = _LinearTrain.forward(ctx, x2, w2d, None, False).view(n, h, wd, cout).permute(0, 3, 1, 2)
+        ks = _conv_ksplit(M, cout, cin) if (_conv1x1_splitk and cin % 4 == 0) else 1
+        ctx.dgrad_ksplit = ks if ks >= _CONV1X1_MIN_PIECES else 1
+        ctx.x_shape = (n, h, wd, cin)
+        return _own_tensor(y)   # NCHW shape over NHWC storage = channels_last
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        n, h, wd, cin = ctx.x_shape
+        dx2, dw, _, _ = _LinearTrain.backward(ctx, dy.permute(0, 2, 3, 1).reshape(n * h * wd, dy.shape[1]))
+        return (None if dx2 is None else dx2.view(n, h, wd, cin).permute(0, 3, 1, 2)), dw, None
+
+
+class _Conv3x3Train(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w_taps, stride, terms):
+        with one_stream():   # a training step: the weight images are rebuilt every step for the stream that uses them next
+            y = conv3x3(x, w_taps, None, False, stride)
+        if y is None:
+            raise _NotApplicable()
+        ctx.stride, ctx.terms = stride, terms
+        ctx.save_for_backward(x, w_taps)
+        return _own_tensor(y)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, w_taps = ctx.saved_tensors
+        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        stride, terms = ctx.stride, ctx.terms
+        n, cin, h, w = x.shape
+        cout = w_taps.shape[0]
+        ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
+        M = n * ho * wo
+        L = _cabi.lib()
+        dyn = dy.permute(0, 2, 3, 1)   # NHWC: the storage of a channels_last gradient
+        if not (dyn.is_contiguous() and dyn.data_ptr() % 16 == 0):
+            dyn = dyn.clone(memory_format=torch.contiguous_format)
+        xn = x.permute(0, 2, 3, 1)     # (contiguous: conv3x3 took x)
+        if xn.data_ptr() % 16:
+            xn = xn.clone(memory_format=torch.contiguous_format)
+        fp32 = dy.dtype == torch.float32
+        own_w = fp32 and cin % 4 == 0 and cout % 4 == 0 and max(M * cout, n * h * w * cin, cout * 9 * cin) * 4 < 0xC0000000
+        own_x = (fp32 and stride == 1 and cout % 64 == 0 and cin % 4 == 0 and (M + 256) * cin * 4 < 0xC0000000
+                 and M * cout * 4 < 0xC0000000)
+        dx = dw = None
+        with torch.cuda.device(dy.device), one_stream():
+            stream = _stream(dy.device)
+            packed_rot = _packed_weight_rot(w_taps, terms) if need_x and own_x else None
+            do_x, do_w = packed_rot is not None, need_w and own_w
+            s_dy = _grad_stats(dyn.view(M, cout), 0, terms, False)[0] if (do_x or do_w) else None
+            if do_x:
+                # the contraction is cut as the forward's is (few pixels under a long K: more workgroups, and no accumulator walks
+                # all 9 Cout products)
+                ksplit = _conv_ksplit(M, 9 * cout, cin, _HALO_KSPLIT_POLICY if _conv_halo else None)
+                dxn = torch.empty((n, h, w, cin), dtype=torch.float32, device=dy.device)
+                wsx = torch.empty((ksplit, M * cin), dtype=torch.float32, device=dy.device) if ksplit > 1 else None
+                rc = L.tf_conv3x3_dgrad_packed_f32(dyn.data_ptr(), s_dy.data_ptr(), packed_rot.data_ptr(), dxn.data_ptr(), _ptr(wsx), ksplit,
+                                                   n, h, w, cin, cout, terms, stream)
+                _cabi.check(rc, "tf_conv3x3_dgrad_packed_f32")
+                dx = dxn.permute(0, 3, 1, 2)
+            if do_w:
+                s_x, _ = _grad_stats(xn.view(n * h * w, cin), 1, terms, False)
+                nbytes = int(L.tf_conv3x3_wgrad_workspace_bytes(n, h, w, cin, cout, stride))
+                ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dy.device)
+                dw = torch.empty((cout, 9 * cin), dtype=torch.float32, device=dy.device)
+                rc = L.tf_conv3x3_wgrad_split_f32(dyn.data_ptr(), xn.data_ptr(), s_dy.data_ptr(), s_x.data_ptr(), dw.data_ptr(), ws.data_ptr(),
+                                                  nbytes, n, h, w, cin, cout, stride, terms, stream)
+                _cabi.check(rc, "tf_conv3x3_wgrad_split_f32")
+            mask = [need_x and not do_x, need_w and not do_w, False]
+            if mask[0] or mask[1]:   # what the kernels do not take: torch, on the same tensors
+                w4 = w_taps.detach().view(cout, 3, 3, cin).permute(0, 3, 1, 2)   # OIHW shape over its channels_last storage
+                tx, tw, _ = torch.ops.aten.convolution_backward(dy, x, w4, None, [stride, stride], [1, 1], [1, 1], False, [0, 0], 1, mask)
+                if mask[0]:
+                    dx = tx
+                if mask[1]:
+                    dw = tw.permute(0, 2, 3, 1).reshape(cout, 9 * cin)
+        if need_x:
+            _conv_train_counts["dgrad_own" if do_x else "dgrad_torch"] += 1
+        if need_w:
+            _conv_train_counts["wgrad_own" if do_w else "wgrad_torch"] += 1
+        return dx, dw, None, None
+
+
+def conv_train(x, w, stride):
+    """A backbone convolution with the library's own backward, or None where the forward kernel declines (the caller keeps F.conv2d).
+    x [N, Cin, H, W]: channels_last, fp32, on the device.
+    w [Cout, 9 Cin] -- the tap-major image `w4.permute(0, 2, 3, 1).reshape(Cout, 9 Cin)` of an OIHW weight, taken OUTSIDE so that autograd
+    carries dw back to the parameter (and through the FrozenBN fold): 3 x 3, padding 1, stride 1 or 2.  The forward IS
+    conv3x3(x, w, None, False, stride); the backward runs tf_linear_grad_stats_f32 on dy, tf_conv3x3_dgrad_packed_f32 (stride 1,
+    Cout % 64 == 0), tf_linear_grad_stats_f32 on x and tf_conv3x3_wgrad_split_f32 (Cin % 4 == 0, Cout % 4 == 0); a gradient whose kernel
+    does not take the call (the input gradient under stride 2, Cout % 64 != 0, misaligned or over-size tensors) is computed by
+    torch.ops.aten.convolution_backward inside the backward.  conv_train_counts() tells which path ran.
+    w [Cout, Cin]: 1 x 1, stride 1, no padding: _LinearTrain on the [N H W, Cin] view of the activation (no bias, residual or ReLU), few
+    pixels under a long contraction cut into pieces as the inference route cuts them (_Conv1x1Train)."""
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and w.dim() == 2 and w.dtype == torch.float32
+            and w.device == x.device):
+        return None
+    y = None
+    n, cin, h, wd = x.shape
+    if x.is_contiguous(memory_format=torch.channels_last) and x.numel() > 0:
+        if w.shape[1] == 9 * cin and stride in (1, 2):
+            try:
+                y = _Conv3x3Train.apply(x, w, stride, _terms())
+            except _NotApplicable:
+                y = None
+        elif w.shape[1] == cin and stride == 1:
+            try:
+                y = _Conv1x1Train.apply(x, w, None)
+            except _NotApplicable:
+                y = None
+            if y is not None and cin % 32:   # (linear() does not take K % 32 != 0: _LinearTrain's forward was F.linear, its backward ran)
+                _conv_train_counts["fwd_torch"] += 1
+                return y
+    _conv_train_counts["fwd_own" if y is not None else "fwd_torch"] += 1
+    return y
 
 
 
