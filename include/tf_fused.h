@@ -419,6 +419,51 @@ int tf_add_layernorm_bwd_f32(const float *dy, const float *x, const float *res, 
                              float *dgamma, float *dbeta, void *workspace, int64_t workspace_bytes, int64_t rows, int C, void *stream);
 
 /*
+ * DROPOUT INSIDE THE TRAINING KERNELS  (trackformer_amd/csrc/dropout_rng.h, dropout_train.h; reference: the nn.Dropout(0.1) in front of
+ * every residual add and behind the feed-forward block's ReLU of models/deformable_transformer.py).  The keep decision of an element is
+ * computed where it is needed, forward and backward, from a counter: no mask and no dropped tensor are stored.
+ *
+ * THE GENERATOR CONTRACT.  Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85).
+ *     key     = (seed low 32 bits, seed high 32 bits)
+ *     counter = (g low, g high, offset low, offset high),   g = i / 4 for element i of the FLAT tensor
+ *     output word j = 0 .. 3 decides element 4 g + j:   kept iff word >= T,   T = floor(p 2^32) computed once by the entry point, in
+ *     double, from the float p;   survivors are multiplied by the float scale = 1.0f / (1.0f - p), dropped elements are exactly 0
+ *     (a select, not a product: also where the operand is inf or NaN).
+ * (seed, offset) = rng[0], rng[1]: an int64[2] tensor ON THE DEVICE that the kernels read -- no host synchronisation, safe inside a
+ * captured graph (the graph replays whatever the tensor holds then).  The decision is an integer comparison and a function of (seed,
+ * offset, p, i) alone: independent of the launch geometry and of the dtype of the data.  Every entry refuses p <= 0, p >= 1 and a
+ * non-finite p with TF_MSDA_ERR_BAD_DIMS.
+ *
+ *   tf_dropout_keep_u8                   keep[k] = 1 / 0 for element first + k, k = 0 .. n - 1 (first and n multiples of 4; keep 4-byte
+ *                                        aligned): the mask itself, for tests and for anyone who wants to look at one.
+ *   tf_add_dropout_layernorm_train_f32   out = LayerNorm(x + keep scale res) gamma + beta, stats[r] = (mean, rstd).  d = keep scale res is
+ *                                        one fp32 product, z = x + d one fp32 addition (never contracted into an fma).  One wave per row,
+ *                                        lane j the float4 chunks j, j + 64, ..., as tf_add_layernorm_f32.  res is required (x itself
+ *                                        is allowed).
+ *   tf_add_dropout_layernorm_bwd_f32     rebuilds z from x, res and the recomputed mask (the forward's bits), then dz as
+ *                                        tf_add_layernorm_bwd_f32.  dx = dz, dres = keep scale dz (exactly 0 where dropped); dx / dres /
+ *                                        dgamma / dbeta may each be NULL.  The column sums follow tf_add_layernorm_bwd_f32 to the letter:
+ *                                        its row blocks (a rule of `rows` alone), its wave order inside a block, its workspace
+ *                                        (tf_add_layernorm_bwd_workspace_bytes) and its second launch.  No atomics, LDS included.
+ *   tf_dropout_inplace_f32               y <- keep scale y over n elements (n % 4 == 0), element i of y is element i of the stream.
+ *   tf_relu_dropout_bwd_f32              out = y > 0 ? dy scale : 0, for y = dropout(relu(h)): scale >= 1 keeps a kept positive
+ *                                        activation positive, so y alone encodes both decisions and the backward needs neither the
+ *                                        generator nor the ReLU output.  y = +-0 and a NaN y give 0.
+ * Gates as tf_add_layernorm_bwd_f32: C % 4 == 0, C <= 4096, rows < 2^31, 16-byte aligned tensors, stats and rng 8-byte aligned; outputs
+ * must not overlap inputs (tf_dropout_inplace_f32 excepted).  Checked in this order before any GPU work: NULL -> TF_MSDA_ERR_NULL_POINTER,
+ * p / dimensions / alignment -> TF_MSDA_ERR_BAD_DIMS, workspace -> TF_MSDA_ERR_WORKSPACE.  Every result is a pure function of the
+ * arguments and of what rng holds: bit-identical from call to call, on any stream and in a captured HIP graph.
+ */
+int tf_dropout_keep_u8(const int64_t *rng, float p, int64_t first, int64_t n, uint8_t *keep, void *stream);
+int tf_add_dropout_layernorm_train_f32(const float *x, const float *res, const float *gamma, const float *beta, const int64_t *rng,
+                                       float p, float *out, float *stats, int64_t rows, int C, float eps, void *stream);
+int tf_add_dropout_layernorm_bwd_f32(const float *dy, const float *x, const float *res, const float *gamma, const float *stats,
+                                     const int64_t *rng, float p, float *dx, float *dres, float *dgamma, float *dbeta, void *workspace,
+                                     int64_t workspace_bytes, int64_t rows, int C, void *stream);
+int tf_dropout_inplace_f32(float *y, const int64_t *rng, float p, int64_t n, void *stream);
+int tf_relu_dropout_bwd_f32(const float *dy, const float *y, float p, float *out, int64_t n, void *stream);
+
+/*
  * THE SET CRITERION AND THE MATCHING COST  (trackformer_amd/csrc/criterion.h; reference: loss_labels_focal / loss_cardinality /
  * loss_boxes of models/detr.py and the focal branch of models/matcher.py, fp32).  The decoder layers' predictions are stacked:
  * logits [L, B, Q, C], boxes [L, B, Q, 4] (cxcywh), contiguous.  tgt_of int32 [L, B, Q] holds the GLOBAL index (into labels / tboxes, the

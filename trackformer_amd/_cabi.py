@@ -73,6 +73,11 @@ EXPORTED_SYMBOLS = (
     "tf_add_layernorm_train_f32",
     "tf_add_layernorm_bwd_workspace_bytes",
     "tf_add_layernorm_bwd_f32",
+    "tf_dropout_keep_u8",
+    "tf_add_dropout_layernorm_train_f32",
+    "tf_add_dropout_layernorm_bwd_f32",
+    "tf_dropout_inplace_f32",
+    "tf_relu_dropout_bwd_f32",
     "tf_set_criterion_fwd_f32",
     "tf_set_criterion_bwd_f32",
     "tf_match_cost_f32",
@@ -88,7 +93,7 @@ EXPORTED_SYMBOLS = (
     "tf_nms_host_f32",
 )
 
-ABI_VERSION = 9   # 9: tf_mask_loss_workspace_bytes / _fwd / _bwd (8: tf_set_criterion_fwd / _bwd, tf_match_cost; 7:tf_add_layernorm_train / _bwd; 6: tf_msda_fused_prologue / _backward_epilogue; 5: tf_linear_grad_stats / wgrad / dgrad; 4: tf_msda_backward_det_* and TF_MSDA_ERR_WORKSPACE; 3: the split-product entry points take w_lo / w_scale / terms)
+ABI_VERSION = 10   # 10: tf_dropout_keep_u8 / _inplace, tf_add_dropout_layernorm_train / _bwd, tf_relu_dropout_bwd (9: tf_mask_loss_workspace_bytes / _fwd / _bwd (8: tf_set_criterion_fwd / _bwd, tf_match_cost; 7:tf_add_layernorm_train / _bwd; 6: tf_msda_fused_prologue / _backward_epilogue; 5: tf_linear_grad_stats / wgrad / dgrad; 4: tf_msda_backward_det_* and TF_MSDA_ERR_WORKSPACE; 3: the split-product entry points take w_lo / w_scale / terms)
 
 _lib = None
 
@@ -236,6 +241,16 @@ def lib():
     L.tf_add_layernorm_bwd_f32.restype = ci
     L.tf_add_layernorm_bwd_f32.argtypes = [vp] * 9 + [i64, i64, ci, vp]
     cf = ctypes.c_float
+    L.tf_dropout_keep_u8.restype = ci
+    L.tf_dropout_keep_u8.argtypes = [vp, cf, i64, i64, vp, vp]
+    L.tf_add_dropout_layernorm_train_f32.restype = ci
+    L.tf_add_dropout_layernorm_train_f32.argtypes = [vp] * 5 + [cf, vp, vp, i64, ci, cf, vp]
+    L.tf_add_dropout_layernorm_bwd_f32.restype = ci
+    L.tf_add_dropout_layernorm_bwd_f32.argtypes = [vp] * 6 + [cf] + [vp] * 5 + [i64, i64, ci, vp]
+    L.tf_dropout_inplace_f32.restype = ci
+    L.tf_dropout_inplace_f32.argtypes = [vp, vp, cf, i64, vp]
+    L.tf_relu_dropout_bwd_f32.restype = ci
+    L.tf_relu_dropout_bwd_f32.argtypes = [vp, vp, cf, vp, i64, vp]
     L.tf_set_criterion_fwd_f32.restype = ci
     L.tf_set_criterion_fwd_f32.argtypes = [vp] * 9 + [ci] * 5 + [cf, cf, cf, vp]
     L.tf_set_criterion_bwd_f32.restype = ci

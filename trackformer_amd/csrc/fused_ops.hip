@@ -9,6 +9,7 @@
 
 #include <atomic>
 
+#include "dropout_rng.h"
 #include "msda_common.h"
 #include "tf_fused.h"
 #include "tf_msda.h"
@@ -140,6 +141,7 @@ bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 
 }  // namespace
 
 #include "layernorm_bwd.h"
+#include "dropout_train.h"
 #include "criterion.h"
 #include "mask_loss.h"
 

@@ -46,6 +46,15 @@ def _ffn_hidden(linear, activation, x, inference):
     return activation(linear(x))
 
 
+def _ffn_hidden_dropped(linear, activation, x, inference, dropout):
+    """dropout(activation(linear(x))).  Opt-in (fused.set_dropout_training): the mask is decided inside the library's kernels."""
+    if not inference:
+        y = fused.dropout_ffn_hidden(x, linear, activation is F.relu, dropout)
+        if y is not None:
+            return y
+    return dropout(_ffn_hidden(linear, activation, x, inference))
+
+
 def _get_clones(module, N):
     return nn.ModuleList([copy.deepcopy(module) for _ in range(N)])
 
@@ -380,8 +389,8 @@ class DeformableTransformerEncoderLayer(nn.Module):
             out = fused.ffn(src, self.linear1, self.linear2, self.norm2, residual=src)
             if out is not None:
                 return out
-        src2 = fused.module_linear(self.linear2, self.dropout2(_ffn_hidden(self.linear1, self.activation, src, inf)), inf)
-        return fused.residual_norm(src, self.dropout3(src2), self.norm2, inf)
+        src2 = fused.module_linear(self.linear2, _ffn_hidden_dropped(self.linear1, self.activation, src, inf, self.dropout2), inf)
+        return fused.residual_norm(src, src2, self.norm2, inf, dropout=self.dropout3)
 
     def forward(self, src, pos, reference_points, spatial_shapes, padding_mask=None):
         inf = _inference(self)
@@ -392,7 +401,7 @@ class DeformableTransformerEncoderLayer(nn.Module):
                                  residual_norm=(src, self.norm1), query_pos=q_pos)
             return self.forward_ffn(src)
         src2 = self.self_attn(q, reference_points, src, spatial_shapes, padding_mask, query_pos=q_pos)
-        src = fused.residual_norm(src, self.dropout1(src2), self.norm1, _inference(self))
+        src = fused.residual_norm(src, src2, self.norm1, _inference(self), dropout=self.dropout1)
         return self.forward_ffn(src)
 
 
@@ -456,8 +465,8 @@ class DeformableTransformerDecoderLayer(nn.Module):
             out = fused.ffn(tgt, self.linear1, self.linear2, self.norm3, residual=tgt)
             if out is not None:
                 return out
-        tgt2 = fused.module_linear(self.linear2, self.dropout3(_ffn_hidden(self.linear1, self.activation, tgt, inf)), inf)
-        return fused.residual_norm(tgt, self.dropout4(tgt2), self.norm3, inf)
+        tgt2 = fused.module_linear(self.linear2, _ffn_hidden_dropped(self.linear1, self.activation, tgt, inf, self.dropout3), inf)
+        return fused.residual_norm(tgt, tgt2, self.norm3, inf, dropout=self.dropout4)
 
     def _self_attention_inference(self, qk_in, v_in, key_padding_mask, residual_norm=None, qk_pos=None):
         """nn.MultiheadAttention(q=k=qk_in, v=v_in) for batch-first inputs without materialising the
@@ -515,7 +524,7 @@ class DeformableTransformerDecoderLayer(nn.Module):
             q = k = self.with_pos_embed(tgt, query_pos)
             tgt2 = self.self_attn(q.transpose(0, 1), k.transpose(0, 1), tgt.transpose(0, 1),
                                   key_padding_mask=key_mask)[0].transpose(0, 1)
-        tgt = tgt2 if normed else fused.residual_norm(tgt, self.dropout2(tgt2), self.norm2, _inference(self))
+        tgt = tgt2 if normed else fused.residual_norm(tgt, tgt2, self.norm2, _inference(self), dropout=self.dropout2)
         # deformable cross attention into the encoder memory
         inf = _inference(self)
         cq, cq_pos = (tgt, query_pos) if (inf and query_pos is not None and fused.pos_add_fused_enabled()) \
@@ -526,7 +535,7 @@ class DeformableTransformerDecoderLayer(nn.Module):
             return self.forward_ffn(tgt)
         tgt2 = self.cross_attn(cq, reference_points, src, src_spatial_shapes, src_padding_mask, query_attn_mask,
                                query_pos=cq_pos, value=src_value)
-        tgt = fused.residual_norm(tgt, self.dropout1(tgt2), self.norm1, _inference(self))
+        tgt = fused.residual_norm(tgt, tgt2, self.norm1, _inference(self), dropout=self.dropout1)
         return self.forward_ffn(tgt)
 
 

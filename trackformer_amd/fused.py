@@ -122,9 +122,16 @@ def add_layernorm(x, res, norm):
     return out
 
 
-def residual_norm(x, res, norm, inference):
+def residual_norm(x, res, norm, inference, dropout=None):
     """norm(x + res): fused on the GPU inference path; with gradients enabled and set_layernorm_training(True) the same kernel with the
-    library's own backward (layernorm_train); plain PyTorch otherwise."""
+    library's own backward (layernorm_train); plain PyTorch otherwise.  dropout: the site's nn.Dropout, norm(x + dropout(res)) -- applied
+    here, at the point the caller used to apply it, unless set_dropout_training() takes the site (dropout_residual_norm)."""
+    if dropout is not None:
+        if not inference:
+            y = dropout_residual_norm(x, res, norm, dropout)
+            if y is not None:
+                return y
+        res = dropout(res)
     if inference:
         y = add_layernorm(x, res, norm)
         if y is not None:
@@ -1519,6 +1526,13 @@ class _LinearTrain(torch.autograd.Function):
             y = F.linear(x, weight, bias)
             if relu:
                 y = torch.relu(y)
+        drop = getattr(ctx, "drop", None)   # (_LinearDropoutTrain: (p, rng), dropout on the fresh ReLU output, in place)
+        if drop is not None:
+            if not (relu and y.is_contiguous() and y.numel() % 4 == 0 and y.data_ptr() % 16 == 0):
+                raise _NotApplicable()
+            with torch.cuda.device(y.device):
+                rc = _cabi.lib().tf_dropout_inplace_f32(y.data_ptr(), drop[1].data_ptr(), drop[0], y.numel(), _stream(y.device))
+            _cabi.check(rc, "tf_dropout_inplace_f32")
         ctx.relu = relu
         ctx.terms = 6 if (_split_terms == 16 and _routed(weight)) else _split_terms
         ctx.save_for_backward(x, weight, y if relu else None)
@@ -1532,7 +1546,17 @@ class _LinearTrain(torch.autograd.Function):
         N, K = weight.shape
         terms = ctx.terms
         dy2 = dy.reshape(-1, N)
-        if ctx.relu:
+        drop = getattr(ctx, "drop", None)
+        if ctx.relu and drop is not None:
+            # y is the dropped-and-scaled activation: positive exactly where the unit was active and kept (scale >= 1)
+            dy2 = dy2 if dy2.is_contiguous() and not dy2.data_ptr() & 15 else dy2.clone(memory_format=torch.contiguous_format)
+            with torch.cuda.device(dy2.device):
+                masked = torch.empty_like(dy2)
+                rc = _cabi.lib().tf_relu_dropout_bwd_f32(dy2.data_ptr(), y.data_ptr(), drop[0], masked.data_ptr(), dy2.numel(),
+                                                         _stream(dy2.device))
+            _cabi.check(rc, "tf_relu_dropout_bwd_f32")
+            dy2 = masked
+        elif ctx.relu:
             dy2 = torch.ops.aten.threshold_backward(dy2, y.reshape(-1, N), 0.0)
         x2 = x.reshape(-1, K)
         dy2 = dy2 if dy2.is_contiguous() and not dy2.data_ptr() & 15 else dy2.clone(memory_format=torch.contiguous_format)
@@ -1583,15 +1607,36 @@ class _LinearTrain(torch.autograd.Function):
         return dx, dw, db, None
 
 
-def linear_train(x, weight, bias=None, relu=False):
+class _LinearDropoutTrain(torch.autograd.Function):
+    """dropout(relu(x @ weight^T + bias)): _LinearTrain with tf_dropout_inplace_f32 behind its forward and tf_relu_dropout_bwd_f32 in place
+    of the ReLU's threshold_backward.  Saves what _LinearTrain saves (x, weight and the one activation tensor)."""
+    @staticmethod
+    def forward(ctx, x, weight, bias, p, rng):
+        ctx.drop = (p, rng)
+        return _LinearTrain.forward(ctx, x, weight, bias, True)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        dx, dw, db, _ = _LinearTrain.backward(ctx, dy)
+        return dx, dw, db, None, None
+
+
+def linear_train(x, weight, bias=None, relu=False, dropout=None):
     """act(x @ weight^T + bias) with the library's own backward: the forward IS linear() (bit-identical to the inference path; None
     where linear() declines the tensors -- host tensors, another dtype, split linears switched off: the caller keeps module(x); a
     shape linear() does not take, K % 32 != 0, is computed by torch inside so that the function never fails for a shape reason), the
     backward runs tf_linear_grad_stats_f32 on dy (with the bias
     gradient) and on x, tf_linear_dgrad_packed_f32 and tf_linear_wgrad_split_f32 (include/tf_fused.h).  A gradient whose kernel does
     not take the shape (K or N not a multiple of 4; the input gradient: N not a multiple of 64) is computed by torch inside the
-    backward: train_route_counts() tells which path ran."""
+    backward: train_route_counts() tells which path ran.
+    dropout (an nn.Dropout in training mode with 0 < p < 1, relu=True only): dropout(relu(.)) with the mask of the library's counter-based
+    generator (include/tf_fused.h: DROPOUT INSIDE THE TRAINING KERNELS); the caller has checked set_dropout_training()."""
     try:
+        if dropout is not None:
+            if not (relu and x.is_cuda and weight.shape[0] % 4 == 0 and _dropout_active(dropout)):
+                return None
+            return _LinearDropoutTrain.apply(x, weight, bias, float(dropout.p), dropout_rng(x.device))
         return _LinearTrain.apply(x, weight, bias, relu)
     except _NotApplicable:
         return None
@@ -1603,7 +1648,7 @@ def linear_train(x, weight, bias=None, relu=False):
 # library's LayerNorm forward, its backward and its two-kernel gamma / beta reduction.  set_layernorm_training(True) /
 # TF_LAYERNORM_TRAIN=1 routes these sites through layernorm_train instead: the forward is the inference kernel (bit-identical to
 # add_layernorm) plus the rows' (mean, rstd), the backward one pass over the rows and a small column reduction -- no atomics,
-# bit-identical from call to call.  Dropout sits before the add and stays a torch op, so the route holds under dropout 0.1.  NOT
+# bit-identical from call to call.  Dropout sits before the add and stays a torch op (unless set_dropout_training, below, takes the site), so the route holds under dropout 0.1.  NOT
 # covered: GroupNorm, the LayerNorm epilogues of the fused inference kernels (linear_residual_norm, ffn), nn.MultiheadAttention's
 # internals.  OFF by default: whether it is faster inside a training step is a measurement (tools/bench_layernorm_train.py,
 # profiles/layernorm_train_bench.json), not a promise.
@@ -1694,6 +1739,16 @@ def layernorm_train(x, res, norm):
     misaligned pointers, a res of another shape / dtype / device.  A non-contiguous res of the right shape (the decoder's transposed
     self-attention output) is copied first, as add_layernorm does on the inference path; the copy is a torch op and differentiable.
     layernorm_train_counts() tells which way the calls went."""
+    ok, res = _layernorm_train_gates(x, res, norm)
+    if not ok:
+        _layernorm_train_counts["torch"] += 1
+        return None
+    _layernorm_train_counts["own"] += 1
+    return _LayerNormTrain.apply(x, res, norm.weight, norm.bias, norm.eps)
+
+
+def _layernorm_train_gates(x, res, norm):
+    """(what the LayerNorm training kernels take, res made contiguous)."""
     ok = (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.numel() > 0 and x.data_ptr() % 16 == 0
           and norm.elementwise_affine and norm.bias is not None and len(norm.normalized_shape) == 1)
     if ok:
@@ -1704,11 +1759,173 @@ def layernorm_train(x, res, norm):
         if ok and not res.is_contiguous():
             res = res.contiguous()   # as add_layernorm: the decoder's self-attention output arrives transposed (a differentiable copy)
         ok = ok and res.data_ptr() % 16 == 0
-    if not ok:
-        _layernorm_train_counts["torch"] += 1
+    return ok, res
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# DROPOUT INSIDE THE TRAINING KERNELS (opt-in; include/tf_fused.h: DROPOUT INSIDE THE TRAINING KERNELS; csrc/dropout_rng.h,
+# csrc/dropout_train.h).  The reference trains with dropout 0.1: every residual_norm() site is norm(x + dropout(res)) and every
+# feed-forward block dropout(relu(linear1(x))), each an ATen dropout that writes a dropped copy and a byte mask and keeps both for the
+# backward.  set_dropout_training(True) / TF_DROPOUT_TRAIN=1 lets the library's kernels decide the mask themselves, from a counter-based
+# generator (Philox4x32-10 on (seed, offset, element index)), forward and backward: no mask and no dropped tensor exist.  It rides on
+# the parent routes: a residual site needs set_layernorm_training (layernorm_train_route), a feed-forward site
+# set_split_linear_training (train_route); a site whose parent route is off, or whose tensors the kernels do not take, runs today's
+# lines (counted *_torch).  (seed, offset) are drawn per site on the device with torch's generator (dropout_rng): torch.manual_seed
+# governs them and a captured graph advances them as it advances torch's own dropout.  "reference" / TF_DROPOUT_TRAIN=reference draws
+# at the same sites in the same order but computes with torch ops and the mask of tf_dropout_keep_u8, in any floating dtype: the oracle
+# of the layer-level test and a debugging aid.  NOT covered: plain DETR's transformer.py, the dropout inside nn.MultiheadAttention, the
+# fused inference epilogues, host tensors, a forward without gradients (the tracking model's previous-frame pass).  OFF by default: whether it is faster inside a training step is a measurement
+# (tools/bench_dropout_train.py, profiles/dropout_train_bench.json), not a promise.
+_dropout_train = None    # None: follow TF_DROPOUT_TRAIN (unset: off); else False / True / "reference"
+_dropout_train_counts = {"ln_own": 0, "ln_torch": 0, "ffn_own": 0, "ffn_torch": 0}
+
+
+def dropout_training_enabled():
+    """False, True or "reference"."""
+    if _dropout_train is not None:
+        return _dropout_train
+    v = os.environ.get("TF_DROPOUT_TRAIN", "0")
+    return "reference" if v == "reference" else v not in ("", "0")
+
+
+def set_dropout_training(flag):
+    """Switch dropout inside the training kernels on or off, or to the torch-op "reference" mode (process-wide; None: follow
+    TF_DROPOUT_TRAIN again); returns the previous setting."""
+    global _dropout_train
+    prev = dropout_training_enabled()
+    _dropout_train = None if flag is None else ("reference" if flag == "reference" else bool(flag))
+    return _switched(prev, dropout_training_enabled())
+
+
+def dropout_train_counts(reset=False):
+    """With the switch on: how many dropout sites in training mode ran the library's own kernels ("ln_own": residual + LayerNorm,
+    "ffn_own": feed-forward hidden activation) and how many kept today's torch ops ("ln_torch", "ffn_torch")."""
+    out = dict(_dropout_train_counts)
+    if reset:
+        for k in _dropout_train_counts:
+            _dropout_train_counts[k] = 0
+    return out
+
+
+def dropout_rng(device):
+    """(seed, offset) of one dropout site: int64[2] on the device, drawn with torch's generator of that device -- no host
+    synchronisation, and inside a captured graph a draw that every replay repeats with fresh values."""
+    return torch.empty(2, dtype=torch.int64, device=device).random_()
+
+
+def dropout_scale(p):
+    """The float 1.0f / (1.0f - p) of the generator contract, as a Python float."""
+    one = torch.ones((), dtype=torch.float32)
+    return float(one / (one - torch.tensor(float(p), dtype=torch.float32)))
+
+
+def dropout_keep(rng, p, n, first=0):
+    """The keep decisions (uint8 [n], 1 = kept) of elements first .. first + n - 1 of the stream `rng` (tf_dropout_keep_u8)."""
+    keep = torch.empty(n, dtype=torch.uint8, device=rng.device)
+    with torch.cuda.device(rng.device):
+        rc = _cabi.lib().tf_dropout_keep_u8(rng.data_ptr(), float(p), first, n, keep.data_ptr(), _stream(rng.device))
+    _cabi.check(rc, "tf_dropout_keep_u8")
+    return keep
+
+
+def _dropout_active(dropout):
+    return dropout.training and 0.0 < dropout.p < 1.0
+
+
+def _reference_factor(t, p):
+    """keep scale for the elements of t (its logical order), in t's dtype: what "reference" mode multiplies with."""
+    keep = dropout_keep(dropout_rng(t.device), p, t.numel()).view(t.shape)
+    return keep.to(t.dtype) * dropout_scale(p)
+
+
+class _DropoutLayerNormTrain(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, res, weight, bias, eps, p, rng):
+        C = x.shape[-1]
+        rows = x.numel() // C
+        with torch.cuda.device(x.device):
+            out = torch.empty_like(x)
+            stats = torch.empty((rows, 2), dtype=torch.float32, device=x.device)
+            rc = _cabi.lib().tf_add_dropout_layernorm_train_f32(x.data_ptr(), res.data_ptr(), weight.data_ptr(), bias.data_ptr(),
+                                                                rng.data_ptr(), p, out.data_ptr(), stats.data_ptr(), rows, C, float(eps),
+                                                                _stream(x.device))
+        _cabi.check(rc, "tf_add_dropout_layernorm_train_f32")
+        ctx.p = p
+        ctx.save_for_backward(x, res, weight, stats, rng)   # no mask, no dropped tensor, no sum
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, res, weight, stats, rng = ctx.saved_tensors
+        need_x, need_res, need_w, need_b = ctx.needs_input_grad[:4]
+        C = x.shape[-1]
+        rows = x.numel() // C
+        dy = dy if dy.is_contiguous() and not dy.data_ptr() & 15 else dy.clone(memory_format=torch.contiguous_format)
+        L = _cabi.lib()
+        dx = dres = dw = db = None
+        with torch.cuda.device(x.device):
+            if need_x:
+                dx = torch.empty_like(x)
+            if need_res:
+                dres = torch.empty_like(x)
+            if need_w:
+                dw = torch.empty_like(weight)
+            if need_b:
+                db = torch.empty_like(weight)
+            nbytes = 0
+            ws = None
+            if need_w or need_b:
+                nbytes = int(L.tf_add_layernorm_bwd_workspace_bytes(rows, C))
+                if nbytes < 0:
+                    _cabi.check(-2, "tf_add_dropout_layernorm_bwd_f32")
+                ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+            if dx is not None or dres is not None or ws is not None:
+                rc = L.tf_add_dropout_layernorm_bwd_f32(dy.data_ptr(), x.data_ptr(), res.data_ptr(), weight.data_ptr(), stats.data_ptr(),
+                                                        rng.data_ptr(), ctx.p, _ptr(dx), _ptr(dres), _ptr(dw), _ptr(db), _ptr(ws), nbytes,
+                                                        rows, C, _stream(x.device))
+                _cabi.check(rc, "tf_add_dropout_layernorm_bwd_f32")
+        return dx, dres, dw, db, None, None, None
+
+
+def dropout_residual_norm(x, res, norm, dropout):
+    """norm(x + dropout(res)) where set_dropout_training() takes the site, else None (the caller applies dropout(res) and goes on as
+    before).  True: tf_add_dropout_layernorm_train_f32 / _bwd_f32 when layernorm_train_route(x) holds, the module is in training mode with
+    0 < p < 1 and the tensors pass layernorm_train's gates (counted ln_own; an active site that is declined: ln_torch).  "reference":
+    torch ops with the mask of tf_dropout_keep_u8, any floating dtype on the device."""
+    mode = dropout_training_enabled()
+    if not mode or not _dropout_active(dropout) or not torch.is_grad_enabled():   # (a forward without gradients keeps torch's dropout, uncounted)
         return None
-    _layernorm_train_counts["own"] += 1
-    return _LayerNormTrain.apply(x, res, norm.weight, norm.bias, norm.eps)
+    if mode == "reference":
+        if not (x.is_cuda and res.is_cuda and res.is_floating_point() and res.numel() > 0 and res.numel() % 4 == 0):
+            return None
+        return norm(x + res * _reference_factor(res, dropout.p))
+    ok = layernorm_train_route(x) and res is not None
+    if ok:
+        ok, res = _layernorm_train_gates(x, res, norm)
+    if not ok:
+        _dropout_train_counts["ln_torch"] += 1
+        return None
+    _dropout_train_counts["ln_own"] += 1
+    return _DropoutLayerNormTrain.apply(x, res, norm.weight, norm.bias, norm.eps, float(dropout.p), dropout_rng(x.device))
+
+
+def dropout_ffn_hidden(x, linear_module, relu, dropout):
+    """dropout(relu(linear(x))) where set_dropout_training() takes the site, else None (the caller runs today's lines).  True:
+    linear_train(..., relu=True, dropout=dropout) when train_route(x) holds (counted ffn_own; an active site that is declined:
+    ffn_torch).  "reference": torch ops with the mask of tf_dropout_keep_u8."""
+    mode = dropout_training_enabled()
+    if not mode or not _dropout_active(dropout) or not torch.is_grad_enabled():   # (a forward without gradients keeps torch's dropout, uncounted)
+        return None
+    if mode == "reference":
+        n = x.numel() // max(x.shape[-1], 1) * linear_module.weight.shape[0]
+        if not (relu and x.is_cuda and x.is_floating_point() and n > 0 and n % 4 == 0):
+            return None
+        y = torch.relu(F.linear(x, linear_module.weight, linear_module.bias))
+        return y * _reference_factor(y, dropout.p)
+    y = linear_train(x, linear_module.weight, linear_module.bias, relu=True, dropout=dropout) if relu and train_route(x) else None
+    _dropout_train_counts["ffn_own" if y is not None else "ffn_torch"] += 1
+    return y
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
