@@ -199,8 +199,9 @@ def test_yardstick_holds_for_the_fp32_formulation_alone(profile):
                            "%s x %s" % (profile, dy_profile))
 
 
-# (1, 4): one lane; (5, 260): 65 chunks; (257, 288): 17 row blocks, the last of one row; (64, 4096): MAXCH 16; (4099, 256): many blocks
-SHAPES = [(1, 4), (5, 260), (257, 288), (64, 4096), (4099, 256)]
+# (1, 4): one lane; (5, 260): 65 chunks; (257, 288): 17 row blocks, the last of one row; (64, 4096): MAXCH 16; (4099, 256): many blocks;
+# (3, 516): 129 chunks, MAXCH 4 with one lane in the third chunk and none in the fourth, fewer rows than a workgroup has waves
+SHAPES = [(1, 4), (5, 260), (257, 288), (64, 4096), (4099, 256), (3, 516)]
 
 
 @emu

@@ -156,8 +156,9 @@ class Pair:
             assert bool((t[n:] == CANARY).all()), "wrote behind " + name
 
 
-# (32769, 256): the first row count with 2048-block rule of more than 16 rows per block
-@pytest.mark.parametrize("rows,C", [(1, 4), (5, 260), (257, 288), (64, 4096), (4099, 256), (32769, 256)])
+# (32769, 256): the first row count with 2048-block rule of more than 16 rows per block; (3, 516): MAXCH 4, one lane in the third chunk
+# and none in the fourth
+@pytest.mark.parametrize("rows,C", [(1, 4), (5, 260), (257, 288), (64, 4096), (4099, 256), (32769, 256), (3, 516)])
 def test_kernels_against_float64(dev, rows, C):
     from trackformer_amd import _cabi
     x, res, gamma, beta, dy = D.operands("unit", "unit", rows, C, rows + C, device=dev)

@@ -120,8 +120,9 @@ def test_yardstick_holds_for_the_fp32_formulation_alone(rows, C, profile):
 
 # ---- the kernels on the emulator -----------------------------------------------------------------------------------------------------
 # (1, 4): one lane, one chunk; (3, 256): fewer rows than a workgroup has waves; (5, 260): 65 chunks, one lane in the second; (5, 288): 72
-# chunks; (2, 4096): MAXCH 16; (257, 256): 17 row blocks, the last of one row
-SHAPES = [(1, 4), (3, 256), (5, 260), (5, 288), (2, 4096), (257, 256)]
+# chunks; (2, 4096): MAXCH 16; (257, 256): 17 row blocks, the last of one row; (3, 516): 129 chunks, MAXCH 4 with one lane in the third
+# chunk and none in the fourth
+SHAPES = [(1, 4), (3, 256), (5, 260), (5, 288), (2, 4096), (257, 256), (3, 516)]
 
 
 @emu

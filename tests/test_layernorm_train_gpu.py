@@ -117,8 +117,9 @@ def run_case(dev, profile, dy_profile, rows, C, with_res):
     return Y.check(b.outputs(), Y.reference(x, res, gamma, dy), Y.fp32_formulation(x, res, gamma, beta, dy), rows, what)
 
 
-# (32768, 256) | (32769, 256): the last row count with 16 rows per block and the first with 2048 blocks of more
-@pytest.mark.parametrize("rows,C", [(1, 4), (5, 260), (257, 288), (4099, 256), (4099, 288), (64, 4096), (32768, 256), (32769, 256)])
+# (32768, 256) | (32769, 256): the last row count with 16 rows per block and the first with 2048 blocks of more; (3, 516): MAXCH 4, one lane
+# in the third chunk and none in the fourth
+@pytest.mark.parametrize("rows,C", [(1, 4), (5, 260), (257, 288), (4099, 256), (4099, 288), (64, 4096), (32768, 256), (32769, 256), (3, 516)])
 def test_kernels_against_float64(dev, rows, C):
     from trackformer_amd import _cabi
     run_case(dev, "unit", "unit", rows, C, with_res=True)

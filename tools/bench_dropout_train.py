@@ -160,13 +160,16 @@ def bench_kernels(iters):
         rows, C, F_ = LN_SHAPES[0][1], LN_SHAPES[0][2], FFN_SHAPE[3]
         # kernel -> algorithmic bytes: forward reads x, res and writes out; backward reads dy, x, res and writes dx, dres; in place reads
         # and writes y; the ReLU + dropout backward reads dy, y and writes out
-        traffic = {"add_dropout_layernorm_kernel": 3 * rows * C * 4, "add_dropout_layernorm_bwd_kernel": 5 * rows * C * 4,
-                   "dropout_inplace_kernel": 2 * rows * F_ * 4, "relu_dropout_bwd_kernel": 3 * rows * F_ * 4}
+        # the backward is add_layernorm_bwd_kernel under its dropout policy: the policy type among the template arguments tells it from the
+        # instantiations without dropout (LnNoDropout), so every part of a key must occur in the profiler's name
+        traffic = {("add_dropout_layernorm_kernel",): 3 * rows * C * 4, ("add_layernorm_bwd_kernel<", "::LnDropout>"): 5 * rows * C * 4,
+                   ("dropout_inplace_kernel",): 2 * rows * F_ * 4, ("relu_dropout_bwd_kernel",): 3 * rows * F_ * 4}
         out = {"calls_per_kernel": iters, "ln_shape": [rows, C], "ffn_hidden_shape": [rows, F_]}
         with open(files[0]) as f:
             for row in csv.DictReader(f):
-                for key, nbytes in traffic.items():
-                    if key in row["Name"]:
+                for parts, nbytes in traffic.items():
+                    if all(part in row["Name"] for part in parts):
+                        key = "".join(parts).replace("::", "")
                         avg_us = float(row["AverageNs"]) / 1e3
                         out[key] = {"name": row["Name"], "calls": int(row["Calls"]), "average_us": round(avg_us, 2),
                                     "min_us": round(float(row["MinNs"]) / 1e3, 2), "max_us": round(float(row["MaxNs"]) / 1e3, 2),

@@ -126,6 +126,8 @@ def bench_kernels(rows, C, iters):
         out = {"rows": rows, "C": C, "calls_per_kernel": iters, "tensor_bytes": rows * C * 4}
         with open(files[0]) as f:
             for row in csv.DictReader(f):
+                if "::LnDropout>" in row["Name"]:   # add_layernorm_bwd_kernel under its dropout policy: tools/bench_dropout_train.py's row
+                    continue
                 for key, tensors in traffic.items():
                     if key + "<" in row["Name"] or (key in row["Name"] and key.endswith("reduce_kernel")):
                         avg_us = float(row["AverageNs"]) / 1e3

@@ -8,6 +8,7 @@
 #include <stdlib.h>
 
 #include <atomic>
+#include <type_traits>
 
 #include "dropout_rng.h"
 #include "msda_common.h"
@@ -136,7 +137,46 @@ add_layernorm_kernel(const float *__restrict__ x, const float *__restrict__ res,
     }
 }
 
+// keep scale v of one 16-byte group (dropout_train.h, layernorm_bwd.h): a select, never a product with 0 (a dropped inf / NaN is 0), and a
+// product the caller cannot contract with its next addition
+__device__ __forceinline__ f32x4_t dropout_apply(f32x4_t v, unsigned bits, float scale)
+{
+#pragma clang fp contract(off)
+    f32x4_t d;
+    d.x = (bits & 1u) ? v.x * scale : 0.f;
+    d.y = (bits & 2u) ? v.y * scale : 0.f;
+    d.z = (bits & 4u) ? v.z * scale : 0.f;
+    d.w = (bits & 8u) ? v.w * scale : 0.f;
+    return d;
+}
+
+__device__ __forceinline__ f32x4_t add_uncontracted(f32x4_t a, f32x4_t b)
+{
+#pragma clang fp contract(off)
+    return a + b;
+}
+
 bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+bool word_aligned8(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
+
+// workgroups of a grid-stride kernel over `items` (`per` of them per 256-thread workgroup): at most 16 workgroups on each of 256 CUs
+long long stream_blocks(long long items, int per = 256)
+{
+    const long long blocks = (items + per - 1) / per;
+    return blocks > 256 * 16 ? 256 * 16 : blocks;
+}
+
+// The row kernels keep a row of C floats in registers, lane j the float4 chunks j, j + 64, ...: f(std::integral_constant<int, MAXCH>)
+// with the smallest MAXCH of 1, 2, 4, 16 that holds the row (C <= 4096).
+template <typename F>
+void with_maxch(int C, F &&f)
+{
+    const int chunks = (C / 4 + 63) / 64;
+    if (chunks <= 1) f(std::integral_constant<int, 1>{});
+    else if (chunks <= 2) f(std::integral_constant<int, 2>{});
+    else if (chunks <= 4) f(std::integral_constant<int, 4>{});
+    else f(std::integral_constant<int, 16>{});
+}
 
 }  // namespace
 
@@ -641,8 +681,7 @@ int tf_bias_act_f32(float *x, const float *bias, const float *residual, int64_t 
         return TF_MSDA_ERR_BAD_DIMS;
     if (residual == x) return TF_MSDA_ERR_BAD_DIMS;   // the kernel's pointers are __restrict__: the residual must not be x itself
     const long long n4 = n / 4;
-    long long blocks = (n4 + 255) / 256;
-    if (blocks > 256 * 16) blocks = 256 * 16;   // grid-stride beyond 16 workgroups per CU
+    const long long blocks = stream_blocks(n4);
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (residual && relu)
         hipLaunchKernelGGL((bias_act_kernel<true, true>), dim3((unsigned)blocks), dim3(256), 0, s, x, bias, residual, n4, C / 4);
@@ -662,24 +701,12 @@ static int add_layernorm_impl(const float *x, const float *res, const float *gam
     if (!aligned16(x) || !aligned16(gamma) || !aligned16(beta) || !aligned16(out) ||
         (res && !aligned16(res)) || (reinterpret_cast<uintptr_t>(stats) & 7))
         return TF_MSDA_ERR_BAD_DIMS;
-    long long blocks = (rows + 3) / 4;   // 4 waves (rows) per 256-thread workgroup
-    if (blocks > 256 * 16) blocks = 256 * 16;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int chunks = (C / 4 + 63) / 64;
-    auto launch = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, s, x, res, gamma, beta, out, stats, (long long)rows, C, eps);
-    };
-    if (stats) {
-        if (chunks <= 1) launch(add_layernorm_kernel<1, true>);
-        else if (chunks <= 2) launch(add_layernorm_kernel<2, true>);
-        else if (chunks <= 4) launch(add_layernorm_kernel<4, true>);
-        else launch(add_layernorm_kernel<16, true>);
-    } else {
-        if (chunks <= 1) launch(add_layernorm_kernel<1, false>);
-        else if (chunks <= 2) launch(add_layernorm_kernel<2, false>);
-        else if (chunks <= 4) launch(add_layernorm_kernel<4, false>);
-        else launch(add_layernorm_kernel<16, false>);
-    }
+    const unsigned blocks = (unsigned)stream_blocks(rows, 4);   // 4 waves (rows) per 256-thread workgroup
+    with_maxch(C, [&](auto maxch) {
+        constexpr int MAXCH = decltype(maxch)::value;
+        hipLaunchKernelGGL((stats ? add_layernorm_kernel<MAXCH, true> : add_layernorm_kernel<MAXCH, false>), dim3(blocks), dim3(256), 0,
+                           static_cast<hipStream_t>(stream), x, res, gamma, beta, out, stats, (long long)rows, C, eps);
+    });
     return hipGetLastError() == hipSuccess ? TF_MSDA_OK : TF_MSDA_ERR_LAUNCH;
 }
 

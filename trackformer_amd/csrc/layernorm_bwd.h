@@ -26,17 +26,26 @@ inline int ln_bwd_blocks(long long rows) { return (int)((rows + ln_bwd_rows_per(
 
 constexpr int kLnRedSlices = 16, kLnRedQuads = 16;   // the reduction's workgroup: 16 slices of the block list x 16 column quads
 
+// What dropout adds to the pass (tf_add_dropout_layernorm_bwd_f32; dropout_train.h): the forward was LayerNorm(x + keep scale res), so z
+// is rebuilt from the recomputed keep decisions and the gradient of res is keep scale dz, a second store.  LnNoDropout is EMPTY and the
+// policy is the kernel's LAST argument: the instantiations without dropout keep the instruction stream they had before the policy existed.
+struct LnNoDropout { static constexpr float *dres = nullptr; };
+struct LnDropout { const long long *rng; unsigned T; float scale; float *dres; };
+
 // Block b walks rows [b rows_per, (b + 1) rows_per); wave w of its four takes rows w, w + 4, ... of them, one row at a time, lane j the
 // float4 chunks j, j + 64, ... as in the forward.  PARTIALS: every lane also sums dy and dy xh of its own columns over the rows its wave
 // walks (registers); waves 1 .. 3 hand theirs to wave 0 through LDS, which adds them in wave order and writes partial[b][0] = sum dy,
-// partial[b][1] = sum dy xh.
-template <int MAXCH, bool PARTIALS>
+// partial[b][1] = sum dy xh.  dz is the gradient of x, and without dropout of res as well (with it: drop.dres; res is never null then).
+template <int MAXCH, bool PARTIALS, typename DROP>
 __global__ void __launch_bounds__(256)
 add_layernorm_bwd_kernel(const float *__restrict__ dy, const float *__restrict__ x, const float *__restrict__ res,
                          const float *__restrict__ gamma, const float *__restrict__ stats, float *__restrict__ dz,
-                         float *__restrict__ partial, long long rows, int C, int rows_per)
+                         float *__restrict__ partial, long long rows, int C, int rows_per, DROP drop)
 {
+    constexpr bool kDrop = std::is_same_v<DROP, LnDropout>;
     __shared__ f32x4_t s_part[3][2][64];   // (PARTIALS) what waves 1 .. 3 hand to wave 0, one chunk at a time
+    [[maybe_unused]] tfd::Stream st;
+    if constexpr (kDrop) st = tfd::load_stream(drop.rng);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int C4 = C >> 2;
     const long long r0 = (long long)blockIdx.x * rows_per;
@@ -54,20 +63,27 @@ add_layernorm_bwd_kernel(const float *__restrict__ dy, const float *__restrict__
     }
     for (long long r = r0 + wave; r < r1; r += 4) {   // (wave-uniform)
         const f32x4_t *xr = reinterpret_cast<const f32x4_t *>(x + r * C);
-        const f32x4_t *rr = res ? reinterpret_cast<const f32x4_t *>(res + r * C) : nullptr;
+        const f32x4_t *rr = kDrop || res ? reinterpret_cast<const f32x4_t *>(res + r * C) : nullptr;
         const f32x4_t *dr = reinterpret_cast<const f32x4_t *>(dy + r * C);
-        const f32x2_t st = reinterpret_cast<const f32x2_t *>(stats)[r];
-        const float mean = st.x, rstd = st.y;
+        const f32x2_t sm = reinterpret_cast<const f32x2_t *>(stats)[r];
+        const float mean = sm.x, rstd = sm.y;
         f32x4_t xh[MAXCH], g[MAXCH];
+        [[maybe_unused]] unsigned bits[MAXCH];   // (kDrop) the keep decisions of the lane's chunks, kept for dres
         float s1 = 0.f, s2 = 0.f;
 #pragma unroll
         for (int k = 0; k < MAXCH; ++k) {
             const int j = lane + k * 64;
             xh[k] = f32x4_t{0.f, 0.f, 0.f, 0.f};
             g[k] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+            if constexpr (kDrop) bits[k] = 0u;
             if (j < C4) {
                 f32x4_t z = xr[j];
-                if (rr) z += rr[j];   // the forward's single fp32 addition
+                if constexpr (kDrop) {
+                    bits[k] = tfd::keep_bits(st, (unsigned long long)(r * C4 + j), drop.T);
+                    z = add_uncontracted(z, dropout_apply(rr[j], bits[k], drop.scale));   // the forward's z, bit for bit
+                } else if (rr) {
+                    z += rr[j];   // the forward's single fp32 addition
+                }
                 const f32x4_t d = dr[j];
                 xh[k] = (z - mean) * rstd;
                 g[k] = ga[k] * d;
@@ -81,12 +97,27 @@ add_layernorm_bwd_kernel(const float *__restrict__ dy, const float *__restrict__
             }
         }
         const float c1 = wave_sum(s1) / (float)C, c2 = wave_sum(s2) / (float)C;
-        if (dz != nullptr) {   // (uniform)
-            f32x4_t *orow = reinterpret_cast<f32x4_t *>(dz + r * C);
+        // The stores are written out per policy on purpose.  One block for both (the row pointer hoisted, the second store under the
+        // policy) compiled to other code on BOTH sides: the instantiations without dropout lost their instruction stream at some MAXCH,
+        // and the dropout ones went from 58 to 68 VGPRs at MAXCH 1 (the hoisted pointer).  As written each side is what it was alone.
+        if constexpr (!kDrop) {
+            if (dz != nullptr) {   // (uniform)
+                f32x4_t *orow = reinterpret_cast<f32x4_t *>(dz + r * C);
+#pragma unroll
+                for (int k = 0; k < MAXCH; ++k) {
+                    const int j = lane + k * 64;
+                    if (j < C4) tfm::stream_store(orow + j, (g[k] - c1 - xh[k] * c2) * rstd);
+                }
+            }
+        } else if (dz != nullptr || drop.dres != nullptr) {   // (uniform)
 #pragma unroll
             for (int k = 0; k < MAXCH; ++k) {
                 const int j = lane + k * 64;
-                if (j < C4) tfm::stream_store(orow + j, (g[k] - c1 - xh[k] * c2) * rstd);
+                if (j < C4) {
+                    const f32x4_t v = (g[k] - c1 - xh[k] * c2) * rstd;
+                    if (dz != nullptr) tfm::stream_store(reinterpret_cast<f32x4_t *>(dz + r * C) + j, v);
+                    if (drop.dres != nullptr) tfm::stream_store(reinterpret_cast<f32x4_t *>(drop.dres + r * C) + j, dropout_apply(v, bits[k], drop.scale));
+                }
             }
         }
     }
@@ -144,16 +175,38 @@ add_layernorm_bwd_reduce_kernel(const float *__restrict__ partial, float *__rest
     }
 }
 
-template <int MAXCH>
-void launch_add_layernorm_bwd(bool partials, unsigned blocks, hipStream_t s, const float *dy, const float *x, const float *res,
-                              const float *gamma, const float *stats, float *dz, float *partial, long long rows, int C, int rows_per)
+// Both backward entries.  own_null / own_bad: what the entry's own arguments (the dropout entry: res, rng, p, dres) add to the first two
+// checks; `name`: what the row pass is noted as.  The checks answer in this order: null pointers, dimensions and alignment, workspace.
+template <typename DROP>
+int add_layernorm_bwd_impl(const char *name, bool own_null, bool own_bad, const float *dy, const float *x, const float *res, const float *gamma,
+                           const float *stats, float *dz, float *dgamma, float *dbeta, void *workspace, int64_t workspace_bytes, int64_t rows,
+                           int C, void *stream, DROP drop)
 {
-    if (partials)
-        hipLaunchKernelGGL((add_layernorm_bwd_kernel<MAXCH, true>), dim3(blocks), dim3(256), 0, s, dy, x, res, gamma, stats, dz, partial, rows, C,
-                           rows_per);
-    else
-        hipLaunchKernelGGL((add_layernorm_bwd_kernel<MAXCH, false>), dim3(blocks), dim3(256), 0, s, dy, x, res, gamma, stats, dz, partial, rows, C,
-                           rows_per);
+    if (own_null || !dy || !x || !gamma || !stats) return TF_MSDA_ERR_NULL_POINTER;
+    if (own_bad || rows <= 0 || rows > 0x7fffffffLL || C <= 0 || (C & 3) || C > 4096) return TF_MSDA_ERR_BAD_DIMS;
+    if (!aligned16(dy) || !aligned16(x) || (res && !aligned16(res)) || !aligned16(gamma) || !word_aligned8(stats) || (dz && !aligned16(dz)) ||
+        (dgamma && !aligned16(dgamma)) || (dbeta && !aligned16(dbeta)))
+        return TF_MSDA_ERR_BAD_DIMS;
+    const bool partials = dgamma != nullptr || dbeta != nullptr;
+    const int nb = ln_bwd_blocks(rows);
+    if (partials && (!workspace || workspace_bytes < (int64_t)nb * 2 * C * 4 || !aligned16(workspace))) return TF_MSDA_ERR_WORKSPACE;
+    if (!partials && dz == nullptr && drop.dres == nullptr) return TF_MSDA_OK;   // nothing asked for
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    float *partial = partials ? static_cast<float *>(workspace) : nullptr;
+    with_maxch(C, [&](auto maxch) {
+        constexpr int MAXCH = decltype(maxch)::value;
+        hipLaunchKernelGGL((partials ? add_layernorm_bwd_kernel<MAXCH, true, DROP> : add_layernorm_bwd_kernel<MAXCH, false, DROP>), dim3((unsigned)nb),
+                           dim3(256), 0, s, dy, x, res, gamma, stats, dz, partial, (long long)rows, C, ln_bwd_rows_per(rows), drop);
+    });
+    if (hipGetLastError() != hipSuccess) return TF_MSDA_ERR_LAUNCH;
+    tfm::note_kernel(name);
+    if (partials) {
+        const dim3 grid((unsigned)((C / 4 + kLnRedQuads - 1) / kLnRedQuads), 2u);
+        hipLaunchKernelGGL(add_layernorm_bwd_reduce_kernel, grid, dim3(256), 0, s, (const float *)partial, dgamma, dbeta, C, nb);
+        if (hipGetLastError() != hipSuccess) return TF_MSDA_ERR_LAUNCH;
+        tfm::note_kernel("add_layernorm_bwd_reduce_f32");
+    }
+    return TF_MSDA_OK;
 }
 
 }  // namespace
@@ -168,32 +221,8 @@ extern "C" int tf_add_layernorm_bwd_f32(const float *dy, const float *x, const f
                                         float *dgamma, float *dbeta, void *workspace, int64_t workspace_bytes, int64_t rows, int C,
                                         void *stream)
 {
-    if (!dy || !x || !gamma || !stats) return TF_MSDA_ERR_NULL_POINTER;
-    if (rows <= 0 || rows > 0x7fffffffLL || C <= 0 || (C & 3) || C > 4096) return TF_MSDA_ERR_BAD_DIMS;
-    if (!aligned16(dy) || !aligned16(x) || (res && !aligned16(res)) || !aligned16(gamma) || (reinterpret_cast<uintptr_t>(stats) & 7) ||
-        (dz && !aligned16(dz)) || (dgamma && !aligned16(dgamma)) || (dbeta && !aligned16(dbeta)))
-        return TF_MSDA_ERR_BAD_DIMS;
-    const bool partials = dgamma != nullptr || dbeta != nullptr;
-    const int nb = ln_bwd_blocks(rows);
-    if (partials && (!workspace || workspace_bytes < (int64_t)nb * 2 * C * 4 || !aligned16(workspace))) return TF_MSDA_ERR_WORKSPACE;
-    if (!partials && dz == nullptr) return TF_MSDA_OK;   // nothing asked for
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    float *partial = partials ? static_cast<float *>(workspace) : nullptr;
-    const int rows_per = ln_bwd_rows_per(rows);
-    const int chunks = (C / 4 + 63) / 64;
-    if (chunks <= 1) launch_add_layernorm_bwd<1>(partials, (unsigned)nb, s, dy, x, res, gamma, stats, dz, partial, (long long)rows, C, rows_per);
-    else if (chunks <= 2) launch_add_layernorm_bwd<2>(partials, (unsigned)nb, s, dy, x, res, gamma, stats, dz, partial, (long long)rows, C, rows_per);
-    else if (chunks <= 4) launch_add_layernorm_bwd<4>(partials, (unsigned)nb, s, dy, x, res, gamma, stats, dz, partial, (long long)rows, C, rows_per);
-    else launch_add_layernorm_bwd<16>(partials, (unsigned)nb, s, dy, x, res, gamma, stats, dz, partial, (long long)rows, C, rows_per);
-    if (hipGetLastError() != hipSuccess) return TF_MSDA_ERR_LAUNCH;
-    tfm::note_kernel("add_layernorm_bwd_f32");
-    if (partials) {
-        const dim3 grid((unsigned)((C / 4 + kLnRedQuads - 1) / kLnRedQuads), 2u);
-        hipLaunchKernelGGL(add_layernorm_bwd_reduce_kernel, grid, dim3(256), 0, s, (const float *)partial, dgamma, dbeta, C, nb);
-        if (hipGetLastError() != hipSuccess) return TF_MSDA_ERR_LAUNCH;
-        tfm::note_kernel("add_layernorm_bwd_reduce_f32");
-    }
-    return TF_MSDA_OK;
+    return add_layernorm_bwd_impl("add_layernorm_bwd_f32", false, false, dy, x, res, gamma, stats, dz, dgamma, dbeta, workspace, workspace_bytes,
+                                  rows, C, stream, LnNoDropout{});
 }
 
 #endif /* TF_LAYERNORM_BWD_H_ */

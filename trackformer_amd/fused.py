@@ -1,7 +1,9 @@
 """Python front-end of the fused element-wise HIP kernels (include/tf_fused.h).
 
-Used by the inference path only (eval mode, gradients disabled) on GPU tensors; everywhere else the
-callers keep the plain PyTorch formulation (these helpers return None when they do not apply)."""
+The first part serves the inference path (eval mode, gradients disabled) on GPU tensors.  The training sections further down (THE
+TRAINING PATH OF ..., DROPOUT INSIDE THE TRAINING KERNELS) are opt-in autograd Functions over the library's own backward kernels, each
+behind a process-wide switch that is off by default.  Everywhere else the callers keep the plain PyTorch formulation (these helpers
+return None when they do not apply)."""
 import os
 import threading
 
@@ -1453,45 +1455,67 @@ def train_route(x):
 
 def train_route_counts(reset=False):
     """How many input / weight / bias gradients of linear_train went to the library's own kernels and how many to torch."""
-    out = dict(_train_counts)
+    return _read_counts(_train_counts, reset)
+
+
+def _read_counts(counts, reset):
+    """A copy of one of the training sections' counters; reset: the counters start again at 0."""
+    out = dict(counts)
     if reset:
-        for k in _train_counts:
-            _train_counts[k] = 0
+        for k in counts:
+            counts[k] = 0
     return out
+
+
+def _aligned(t):
+    """t where the kernels can read it as it is (contiguous, 16-byte aligned), else a contiguous copy."""
+    return t if t.is_contiguous() and not t.data_ptr() & 15 else t.clone(memory_format=torch.contiguous_format)
+
+
+def _route_terms(weight):
+    """The terms a backward runs with: those of the forward (a layer routed to six terms while the default is the fp16 product)."""
+    return 6 if (_split_terms == 16 and _routed(weight)) else _split_terms
 
 
 class _NotApplicable(Exception):
     pass
 
 
-def _packed_weight_t(weight, terms):
-    """Fragment-order image of weight^T (the `weight` of the input gradient dx = dy . w), cached on the parameter under its
-    source_key() like _packed_weight; None when it cannot be built (shape; stream capture without a cached image)."""
-    cache = getattr(weight, "_tf_packed_t", None)
-    key = source_key(weight)
+def _packed_image(t, attr, rows, cols, terms, source):
+    """Fragment-order image (tf_linear_pack_weight_f32) of the contiguous [rows, cols] tensor source() derives from t, cached on t as
+    `attr` under its source_key(), per `terms`; None when it cannot be built (shape; stream capture without a cached image).  The
+    images of the training path only: no publish barrier, the stream that built an image is remembered instead."""
+    cache = getattr(t, attr, None)
+    key = source_key(t)
     if cache is None or cache[0] != key:
         cache = (key, {})
-        weight._tf_packed_t = cache
+        setattr(t, attr, cache)
     capturing = torch.cuda.is_current_stream_capturing()
     hit = cache[1].get(terms)
     if hit is None:
         if capturing:
             return None   # never build a cached buffer inside a graph's memory pool
-        N, K = weight.shape
-        nbytes = _cabi.lib().tf_linear_packed_bytes(N, K, terms)
+        nbytes = _cabi.lib().tf_linear_packed_bytes(rows, cols, terms)
         if nbytes <= 0:
             return None
-        with torch.cuda.device(weight.device):
-            wt = weight.detach().t().contiguous()
-            buf = torch.empty(nbytes, dtype=torch.uint8, device=weight.device)
-            rc = _cabi.lib().tf_linear_pack_weight_f32(wt.data_ptr(), buf.data_ptr(), N, K, terms, _stream(weight.device))
+        with torch.cuda.device(t.device):
+            src = source()
+            buf = torch.empty(nbytes, dtype=torch.uint8, device=t.device)
+            rc = _cabi.lib().tf_linear_pack_weight_f32(src.data_ptr(), buf.data_ptr(), rows, cols, terms, _stream(t.device))
         _cabi.check(rc, "tf_linear_pack_weight_f32")
-        hit = (buf, torch.cuda.current_stream(weight.device))
+        hit = (buf, torch.cuda.current_stream(t.device))
         cache[1][terms] = hit
-    elif not capturing and hit[1] != torch.cuda.current_stream(weight.device):
+    elif not capturing and hit[1] != torch.cuda.current_stream(t.device):
         # built on another stream (a training step rebuilds it for the stream that runs the backward: no host synchronisation)
-        torch.cuda.current_stream(weight.device).wait_stream(hit[1])
+        torch.cuda.current_stream(t.device).wait_stream(hit[1])
     return hit[0]
+
+
+def _packed_weight_t(weight, terms):
+    """Fragment-order image of weight^T (the `weight` of the input gradient dx = dy . w), cached on the parameter under its
+    source_key() like _packed_weight; None when it cannot be built (shape; stream capture without a cached image)."""
+    N, K = weight.shape
+    return _packed_image(weight, "_tf_packed_t", N, K, terms, lambda: weight.detach().t().contiguous())
 
 
 def _grad_stats(a, role, terms, colsum):
@@ -1534,7 +1558,7 @@ class _LinearTrain(torch.autograd.Function):
                 rc = _cabi.lib().tf_dropout_inplace_f32(y.data_ptr(), drop[1].data_ptr(), drop[0], y.numel(), _stream(y.device))
             _cabi.check(rc, "tf_dropout_inplace_f32")
         ctx.relu = relu
-        ctx.terms = 6 if (_split_terms == 16 and _routed(weight)) else _split_terms
+        ctx.terms = _route_terms(weight)
         ctx.save_for_backward(x, weight, y if relu else None)
         return y
 
@@ -1549,7 +1573,7 @@ class _LinearTrain(torch.autograd.Function):
         drop = getattr(ctx, "drop", None)
         if ctx.relu and drop is not None:
             # y is the dropped-and-scaled activation: positive exactly where the unit was active and kept (scale >= 1)
-            dy2 = dy2 if dy2.is_contiguous() and not dy2.data_ptr() & 15 else dy2.clone(memory_format=torch.contiguous_format)
+            dy2 = _aligned(dy2)
             with torch.cuda.device(dy2.device):
                 masked = torch.empty_like(dy2)
                 rc = _cabi.lib().tf_relu_dropout_bwd_f32(dy2.data_ptr(), y.data_ptr(), drop[0], masked.data_ptr(), dy2.numel(),
@@ -1559,8 +1583,7 @@ class _LinearTrain(torch.autograd.Function):
         elif ctx.relu:
             dy2 = torch.ops.aten.threshold_backward(dy2, y.reshape(-1, N), 0.0)
         x2 = x.reshape(-1, K)
-        dy2 = dy2 if dy2.is_contiguous() and not dy2.data_ptr() & 15 else dy2.clone(memory_format=torch.contiguous_format)
-        x2 = x2 if x2.is_contiguous() and not x2.data_ptr() & 15 else x2.clone(memory_format=torch.contiguous_format)
+        dy2, x2 = _aligned(dy2), _aligned(x2)
         M = dy2.shape[0]
         L = _cabi.lib()
         own = K % 4 == 0 and N % 4 == 0 and max(M * N, M * K, N * K) * 4 < 0xC0000000 and dy2.dtype == torch.float32
@@ -1679,56 +1702,83 @@ def layernorm_train_route(x):
 def layernorm_train_counts(reset=False):
     """How many layernorm_train calls ran the library's own kernels ("own") and how many were declined ("torch": the caller kept
     norm(x + res))."""
-    out = dict(_layernorm_train_counts)
-    if reset:
-        for k in _layernorm_train_counts:
-            _layernorm_train_counts[k] = 0
+    return _read_counts(_layernorm_train_counts, reset)
+
+
+def _layernorm_train_forward(ctx, x, res, weight, bias, eps, drop=None):
+    """The forward of both LayerNorm Functions.  drop: None | (p, rng), the residual dropped inside the kernel (res is a tensor then)."""
+    C = x.shape[-1]
+    rows = x.numel() // C
+    L = _cabi.lib()
+    with torch.cuda.device(x.device):
+        out = torch.empty_like(x)
+        stats = torch.empty((rows, 2), dtype=torch.float32, device=x.device)
+        tail = (out.data_ptr(), stats.data_ptr(), rows, C, float(eps), _stream(x.device))
+        if drop is None:
+            name = "tf_add_layernorm_train_f32"
+            rc = L.tf_add_layernorm_train_f32(x.data_ptr(), _ptr(res), weight.data_ptr(), bias.data_ptr(), *tail)
+        else:
+            name = "tf_add_dropout_layernorm_train_f32"
+            rc = L.tf_add_dropout_layernorm_train_f32(x.data_ptr(), res.data_ptr(), weight.data_ptr(), bias.data_ptr(), drop[1].data_ptr(),
+                                                      drop[0], *tail)
+    _cabi.check(rc, name)
+    # what torch keeps for this chain, and (seed, offset) under dropout: no sum, no normalised activation, no mask, no dropped tensor
+    if drop is None:
+        ctx.save_for_backward(x, res, weight, stats)
+    else:
+        ctx.p = drop[0]
+        ctx.save_for_backward(x, res, weight, stats, drop[1])
     return out
+
+
+def _layernorm_train_backward(ctx, dy):
+    """The backward of both: the gradients of (x, res, weight, bias).  Without dropout ONE tensor is the gradient of x and of res; with
+    it dres = keep scale dx is a tensor of its own.  Nothing is launched when nothing is needed."""
+    x, res, weight, stats, *rng = ctx.saved_tensors
+    need_x, need_res, need_w, need_b = ctx.needs_input_grad[:4]
+    C = x.shape[-1]
+    rows = x.numel() // C
+    dy = _aligned(dy)
+    L = _cabi.lib()
+    name = "tf_add_dropout_layernorm_bwd_f32" if rng else "tf_add_layernorm_bwd_f32"
+    dx = dres = dw = db = ws = None
+    nbytes = 0
+    with torch.cuda.device(x.device):
+        if need_x or (need_res and not rng):
+            dx = torch.empty_like(x)
+        if need_res and rng:
+            dres = torch.empty_like(x)
+        if need_w:
+            dw = torch.empty_like(weight)
+        if need_b:
+            db = torch.empty_like(weight)
+        if need_w or need_b:
+            nbytes = int(L.tf_add_layernorm_bwd_workspace_bytes(rows, C))
+            if nbytes < 0:
+                _cabi.check(-2, name)
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        if dx is not None or dres is not None or ws is not None:
+            head = (dy.data_ptr(), x.data_ptr(), _ptr(res), weight.data_ptr(), stats.data_ptr())
+            tail = (_ptr(dw), _ptr(db), _ptr(ws), nbytes, rows, C, _stream(x.device))
+            if rng:
+                rc = L.tf_add_dropout_layernorm_bwd_f32(*head, rng[0].data_ptr(), ctx.p, _ptr(dx), _ptr(dres), *tail)
+            else:
+                rc = L.tf_add_layernorm_bwd_f32(*head, _ptr(dx), *tail)
+            _cabi.check(rc, name)
+    if not rng:
+        dres = dx
+    return (dx if need_x else None), (dres if need_res else None), dw, db
 
 
 class _LayerNormTrain(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, res, weight, bias, eps):
-        C = x.shape[-1]
-        rows = x.numel() // C
-        with torch.cuda.device(x.device):
-            out = torch.empty_like(x)
-            stats = torch.empty((rows, 2), dtype=torch.float32, device=x.device)
-            rc = _cabi.lib().tf_add_layernorm_train_f32(x.data_ptr(), _ptr(res), weight.data_ptr(), bias.data_ptr(), out.data_ptr(),
-                                                        stats.data_ptr(), rows, C, float(eps), _stream(x.device))
-        _cabi.check(rc, "tf_add_layernorm_train_f32")
-        ctx.save_for_backward(x, res, weight, stats)   # what torch keeps for this chain: no sum, no normalised activation
-        return out
+        return _layernorm_train_forward(ctx, x, res, weight, bias, eps)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, dy):
-        x, res, weight, stats = ctx.saved_tensors
-        need_x, need_res, need_w, need_b = ctx.needs_input_grad[:4]
-        C = x.shape[-1]
-        rows = x.numel() // C
-        dy = dy if dy.is_contiguous() and not dy.data_ptr() & 15 else dy.clone(memory_format=torch.contiguous_format)
-        L = _cabi.lib()
-        dz = dw = db = None
-        with torch.cuda.device(x.device):
-            if need_x or need_res:
-                dz = torch.empty_like(x)
-            if need_w:
-                dw = torch.empty_like(weight)
-            if need_b:
-                db = torch.empty_like(weight)
-            nbytes = 0
-            ws = None
-            if need_w or need_b:
-                nbytes = int(L.tf_add_layernorm_bwd_workspace_bytes(rows, C))
-                if nbytes < 0:
-                    _cabi.check(-2, "tf_add_layernorm_bwd_f32")
-                ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-            if dz is not None or ws is not None:
-                rc = L.tf_add_layernorm_bwd_f32(dy.data_ptr(), x.data_ptr(), _ptr(res), weight.data_ptr(), stats.data_ptr(), _ptr(dz), _ptr(dw),
-                                                _ptr(db), _ptr(ws), nbytes, rows, C, _stream(x.device))
-                _cabi.check(rc, "tf_add_layernorm_bwd_f32")
-        return (dz if need_x else None), (dz if need_res else None), dw, db, None
+        return _layernorm_train_backward(ctx, dy) + (None,)
 
 
 def layernorm_train(x, res, norm):
@@ -1800,11 +1850,7 @@ def set_dropout_training(flag):
 def dropout_train_counts(reset=False):
     """With the switch on: how many dropout sites in training mode ran the library's own kernels ("ln_own": residual + LayerNorm,
     "ffn_own": feed-forward hidden activation) and how many kept today's torch ops ("ln_torch", "ffn_torch")."""
-    out = dict(_dropout_train_counts)
-    if reset:
-        for k in _dropout_train_counts:
-            _dropout_train_counts[k] = 0
-    return out
+    return _read_counts(_dropout_train_counts, reset)
 
 
 def dropout_rng(device):
@@ -1841,51 +1887,12 @@ def _reference_factor(t, p):
 class _DropoutLayerNormTrain(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, res, weight, bias, eps, p, rng):
-        C = x.shape[-1]
-        rows = x.numel() // C
-        with torch.cuda.device(x.device):
-            out = torch.empty_like(x)
-            stats = torch.empty((rows, 2), dtype=torch.float32, device=x.device)
-            rc = _cabi.lib().tf_add_dropout_layernorm_train_f32(x.data_ptr(), res.data_ptr(), weight.data_ptr(), bias.data_ptr(),
-                                                                rng.data_ptr(), p, out.data_ptr(), stats.data_ptr(), rows, C, float(eps),
-                                                                _stream(x.device))
-        _cabi.check(rc, "tf_add_dropout_layernorm_train_f32")
-        ctx.p = p
-        ctx.save_for_backward(x, res, weight, stats, rng)   # no mask, no dropped tensor, no sum
-        return out
+        return _layernorm_train_forward(ctx, x, res, weight, bias, eps, drop=(p, rng))
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, dy):
-        x, res, weight, stats, rng = ctx.saved_tensors
-        need_x, need_res, need_w, need_b = ctx.needs_input_grad[:4]
-        C = x.shape[-1]
-        rows = x.numel() // C
-        dy = dy if dy.is_contiguous() and not dy.data_ptr() & 15 else dy.clone(memory_format=torch.contiguous_format)
-        L = _cabi.lib()
-        dx = dres = dw = db = None
-        with torch.cuda.device(x.device):
-            if need_x:
-                dx = torch.empty_like(x)
-            if need_res:
-                dres = torch.empty_like(x)
-            if need_w:
-                dw = torch.empty_like(weight)
-            if need_b:
-                db = torch.empty_like(weight)
-            nbytes = 0
-            ws = None
-            if need_w or need_b:
-                nbytes = int(L.tf_add_layernorm_bwd_workspace_bytes(rows, C))
-                if nbytes < 0:
-                    _cabi.check(-2, "tf_add_dropout_layernorm_bwd_f32")
-                ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-            if dx is not None or dres is not None or ws is not None:
-                rc = L.tf_add_dropout_layernorm_bwd_f32(dy.data_ptr(), x.data_ptr(), res.data_ptr(), weight.data_ptr(), stats.data_ptr(),
-                                                        rng.data_ptr(), ctx.p, _ptr(dx), _ptr(dres), _ptr(dw), _ptr(db), _ptr(ws), nbytes,
-                                                        rows, C, _stream(x.device))
-                _cabi.check(rc, "tf_add_dropout_layernorm_bwd_f32")
-        return dx, dres, dw, db, None, None, None
+        return _layernorm_train_backward(ctx, dy) + (None, None, None)
 
 
 def dropout_residual_norm(x, res, norm, dropout):
@@ -1942,11 +1949,7 @@ def conv_train_counts(reset=False):
     """How conv_train's calls went: forwards it ran (fwd_own) or declined on device tensors (fwd_torch: the caller's F.conv2d), and
     the input / weight gradients of its 3 x 3 calls by the library's own kernels or by torch.  (The gradients of the 1 x 1 calls are
     linear_train's: train_route_counts().)"""
-    out = dict(_conv_train_counts)
-    if reset:
-        for k in _conv_train_counts:
-            _conv_train_counts[k] = 0
-    return out
+    return _read_counts(_conv_train_counts, reset)
 
 
 def _packed_weight_rot(w_taps, terms):
@@ -1955,30 +1958,9 @@ def _packed_weight_rot(w_taps, terms):
     built (shape; stream capture without a cached image).  The cache serves a weight tensor that persists; backbone._conv_bn hands
     conv_train a new image of the folded weight every step, so there the image is packed once per call, and a training step captured
     into a HIP graph finds none: its 3 x 3 input gradients are torch's (counted in conv_train_counts)."""
-    cache = getattr(w_taps, "_tf_packed_rot", None)
-    key = source_key(w_taps)
-    if cache is None or cache[0] != key:
-        cache = (key, {})
-        w_taps._tf_packed_rot = cache
-    capturing = torch.cuda.is_current_stream_capturing()
-    hit = cache[1].get(terms)
-    if hit is None:
-        if capturing:
-            return None   # never build a cached buffer inside a graph's memory pool
-        cout, cin = w_taps.shape[0], w_taps.shape[1] // 9
-        nbytes = _cabi.lib().tf_linear_packed_bytes(9 * cout, cin, terms)
-        if nbytes <= 0:
-            return None
-        with torch.cuda.device(w_taps.device):
-            wr = w_taps.detach().view(cout, 3, 3, cin).flip(1, 2).permute(3, 1, 2, 0).contiguous()
-            buf = torch.empty(nbytes, dtype=torch.uint8, device=w_taps.device)
-            rc = _cabi.lib().tf_linear_pack_weight_f32(wr.data_ptr(), buf.data_ptr(), 9 * cout, cin, terms, _stream(w_taps.device))
-        _cabi.check(rc, "tf_linear_pack_weight_f32")
-        hit = (buf, torch.cuda.current_stream(w_taps.device))
-        cache[1][terms] = hit
-    elif not capturing and hit[1] != torch.cuda.current_stream(w_taps.device):
-        torch.cuda.current_stream(w_taps.device).wait_stream(hit[1])
-    return hit[0]
+    cout, cin = w_taps.shape[0], w_taps.shape[1] // 9
+    return _packed_image(w_taps, "_tf_packed_rot", 9 * cout, cin, terms,
+                         lambda: w_taps.detach().view(cout, 3, 3, cin).flip(1, 2).permute(3, 1, 2, 0).contiguous())
 
 
 def _own_tensor(v):
@@ -2005,7 +1987,7 @@ class _Conv1x1Train(torch.autograd.Function):
                 y = conv3x3(x, w2d, None, False, 1)
         if y is not None:
             ctx.relu = False
-            ctx.terms = 6 if (_split_terms == 16 and _routed(w2d)) else _split_terms
+            ctx.terms = _route_terms(w2d)
             ctx.save_for_backward(x2, w2d, None)
         else:
             y = _LinearTrain.forward(ctx, x2, w2d, None, False).view(n, h, wd, cout).permute(0, 3, 1, 2)
@@ -2044,9 +2026,7 @@ class _Conv3x3Train(torch.autograd.Function):
         ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
         M = n * ho * wo
         L = _cabi.lib()
-        dyn = dy.permute(0, 2, 3, 1)   # NHWC: the storage of a channels_last gradient
-        if not (dyn.is_contiguous() and dyn.data_ptr() % 16 == 0):
-            dyn = dyn.clone(memory_format=torch.contiguous_format)
+        dyn = _aligned(dy.permute(0, 2, 3, 1))   # NHWC: the storage of a channels_last gradient
         xn = x.permute(0, 2, 3, 1)     # (contiguous: conv3x3 took x)
         if xn.data_ptr() % 16:
             xn = xn.clone(memory_format=torch.contiguous_format)
