@@ -95,6 +95,36 @@ int tf_groupnorm_relu_nhwc_f32(const float *x, const float *gamma, const float *
                                int HW, int C, int G, float eps, int64_t x_image_stride, int64_t out_image_stride, void *stream);
 
 /*
+ * GroupNorm of up to 8 pyramid levels in TWO launches, written into one token buffer: out [N, S, C] (image n at out + n *
+ * out_image_stride floats), level l normalised into the rows row0 .. row0 + HW - 1 of every image -- the reference's input projections
+ * followed by the flatten + concatenation in front of the encoder (models/deformable_detr.py:73-90, models/deformable_transformer.py:
+ * 139-156).  Per level:
+ *   pieces == 1   src is y [N, HW, C] (dense: image n at src + n HW C), read by both passes; bias is ignored
+ *   pieces  > 1   src holds the split-K partial sums [pieces][N HW C] a GEMM left behind (tf_conv_packed_partials_f32).  The statistics
+ *                 pass forms y = ((p0 + p1) + ... + p_last) + bias -- the order of the GEMM's own second pass: bit-identical y --, stores
+ *                 it at the level's output rows, and the second pass normalises it in place.  bias [C] or NULL.
+ * Statistics as tf_groupnorm_nhwc_f32 (every element widened to double before it is squared and summed; biased variance, clamped at
+ * 0; rstd = 1 / sqrt(var + eps) in double), but summed in a fixed order without atomics: two calls give the same bits.  Every
+ * operation is rounded on its own (no fused multiply-add).  workspace: tf_groupnorm_levels_workspace_doubles(...) doubles, 16-byte
+ * aligned, every one written by the call (nothing to clear); -1 for arguments the entry rejects.
+ * C % 4 == 0, C <= 1024, G <= 256 dividing C, N <= 65535, out_image_stride % 4 == 0 and >= (row0 + HW) C for every level; the levels'
+ * row ranges must not overlap and no src may lie inside out; 16-byte aligned pointers.  The table is read during the call.
+ * NULL pointer -> TF_MSDA_ERR_NULL_POINTER, then dimensions / alignment -> TF_MSDA_ERR_BAD_DIMS, before any GPU work.
+ */
+typedef struct tf_gn_level {
+    const float *src;
+    const float *bias;
+    const float *gamma;
+    const float *beta;
+    int pieces;
+    int HW;
+    int64_t row0;
+} tf_gn_level;
+int64_t tf_groupnorm_levels_workspace_doubles(const tf_gn_level *levels, int nlevels, int N, int C, int G);
+int tf_groupnorm_levels_nhwc_f32(const tf_gn_level *levels, int nlevels, int N, int C, int G, float eps, float *out,
+                                 int64_t out_image_stride, double *workspace, void *stream);
+
+/*
  * The FPN merge of the mask head in one pass (reference: models/detr_segmentation.py:142-156 `_expand(adapter(fpn), Q) +
  * F.interpolate(x, size=fpn.shape[-2:], mode="nearest")`): out[n, y, x, c] = low[n, ys, xs, c] + fpn[n / q_per_image, y, x, c] with
  * ys = min(floorf(y * (float)h / H), h - 1), xs likewise (torch's legacy "nearest" index).  low [N, h, w, C], fpn [N / q_per_image, H,
@@ -574,6 +604,15 @@ int tf_mask_loss_bwd_f32(const float *G, const float *src, const uint8_t *tgt, c
 int tf_conv_packed_f32(const float *x, const void *w_packed, const float *bias, const float *residual, float *y, float *workspace,
                        int ksplit, int nimg, int hin, int win, int cin, int cout, int ks, int stride, int relu, int terms,
                        void *stream);
+/*
+ * The same convolution with its split-K second pass DEFERRED to the consumer (tf_groupnorm_levels_nhwc_f32 adds the pieces in its
+ * own fetch): only the GEMM launch runs.  *pieces = the number of partial sums [pieces][M * cout] it left in `workspace` (what the
+ * launch code made of `ksplit` for this shape), in the order the second pass would add them, WITHOUT the bias; *pieces == 1: the
+ * launch was not split and workspace holds the finished y, bias added.  No residual, no ReLU.  workspace: max(ksplit, 1) * M * cout
+ * floats, always required; otherwise the arguments and checks of tf_conv_packed_f32 with ksplit > 1.
+ */
+int tf_conv_packed_partials_f32(const float *x, const void *w_packed, const float *bias, float *workspace, int ksplit, int nimg, int hin,
+                                int win, int cin, int cout, int ks, int stride, int terms, int *pieces, void *stream);
 
 /*
  * The feed-forward block of a transformer layer in one launch (trackformer_amd/csrc/ffn_fused.hip):

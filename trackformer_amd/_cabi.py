@@ -89,11 +89,14 @@ EXPORTED_SYMBOLS = (
     "tf_linear_res_ln_f32",
     "tf_linear_groups_f32",
     "tf_conv_packed_f32",
+    "tf_conv_packed_partials_f32",
+    "tf_groupnorm_levels_workspace_doubles",
+    "tf_groupnorm_levels_nhwc_f32",
     "tf_mha_core_f32",
     "tf_nms_host_f32",
 )
 
-ABI_VERSION = 10   # 10: tf_dropout_keep_u8 / _inplace, tf_add_dropout_layernorm_train / _bwd, tf_relu_dropout_bwd (9: tf_mask_loss_workspace_bytes / _fwd / _bwd (8: tf_set_criterion_fwd / _bwd, tf_match_cost; 7:tf_add_layernorm_train / _bwd; 6: tf_msda_fused_prologue / _backward_epilogue; 5: tf_linear_grad_stats / wgrad / dgrad; 4: tf_msda_backward_det_* and TF_MSDA_ERR_WORKSPACE; 3: the split-product entry points take w_lo / w_scale / terms)
+ABI_VERSION = 11   # 11: tf_groupnorm_levels_nhwc_f32 / _workspace_doubles, tf_conv_packed_partials_f32 (10: tf_dropout_keep_u8 / _inplace, tf_add_dropout_layernorm_train / _bwd, tf_relu_dropout_bwd (9: tf_mask_loss_workspace_bytes / _fwd / _bwd (8: tf_set_criterion_fwd / _bwd, tf_match_cost; 7:tf_add_layernorm_train / _bwd; 6: tf_msda_fused_prologue / _backward_epilogue; 5: tf_linear_grad_stats / wgrad / dgrad; 4: tf_msda_backward_det_* and TF_MSDA_ERR_WORKSPACE; 3: the split-product entry points take w_lo / w_scale / terms)
 
 _lib = None
 
@@ -102,6 +105,12 @@ class ProjGroup(ctypes.Structure):
     """tf_proj_group of include/tf_fused.h (tf_linear_groups_f32)."""
     _fields_ = [("w_packed", ctypes.c_void_p), ("bias", ctypes.c_void_p), ("y", ctypes.c_void_p), ("N", ctypes.c_int),
                 ("add_x2", ctypes.c_int)]
+
+
+class GnLevel(ctypes.Structure):
+    """tf_gn_level of include/tf_fused.h (tf_groupnorm_levels_nhwc_f32)."""
+    _fields_ = [("src", ctypes.c_void_p), ("bias", ctypes.c_void_p), ("gamma", ctypes.c_void_p), ("beta", ctypes.c_void_p),
+                ("pieces", ctypes.c_int), ("HW", ctypes.c_int), ("row0", ctypes.c_int64)]
 
 
 class MSDAError(RuntimeError):
@@ -265,6 +274,12 @@ def lib():
     L.tf_mask_loss_bwd_f32.argtypes = [vp] * 7 + [ci] * 7 + [cf, cf, cf, vp]
     L.tf_conv_packed_f32.restype = ci
     L.tf_conv_packed_f32.argtypes = [vp, vp, vp, vp, vp, vp] + [ci] * 10 + [vp]
+    L.tf_conv_packed_partials_f32.restype = ci
+    L.tf_conv_packed_partials_f32.argtypes = [vp, vp, vp, vp] + [ci] * 9 + [ctypes.POINTER(ci), vp]
+    L.tf_groupnorm_levels_workspace_doubles.restype = i64
+    L.tf_groupnorm_levels_workspace_doubles.argtypes = [ctypes.POINTER(GnLevel), ci, ci, ci, ci]
+    L.tf_groupnorm_levels_nhwc_f32.restype = ci
+    L.tf_groupnorm_levels_nhwc_f32.argtypes = [ctypes.POINTER(GnLevel), ci, ci, ci, ci, ctypes.c_float, vp, i64, vp, vp]
     L.tf_mha_core_f32.restype = ci
     L.tf_mha_core_f32.argtypes = [vp, vp, vp, vp, vp] + [ci] * 9 + [ctypes.c_float, vp]
     if L.tf_msda_abi_version() != ABI_VERSION:

@@ -99,7 +99,7 @@ def _build_tools(force, verbose):
     out_dir = os.path.join(REPO_DIR, "tools", "bin")
     lib = os.path.join(LIB_DIR, "libtf_msda.so")
     built = []
-    for name in ("msda_bench", "linear_bench", "ffn_bench", "proj_groups_bench"):
+    for name in ("msda_bench", "linear_bench", "ffn_bench", "proj_groups_bench", "gn_levels_bench"):
         src = os.path.join(REPO_DIR, "tools", name + ".cpp")
         if not os.path.exists(src):
             continue

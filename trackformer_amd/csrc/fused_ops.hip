@@ -297,6 +297,201 @@ groupnorm_apply_kernel(const float *__restrict__ x, const double *__restrict__ w
     }
 }
 
+// ---- GroupNorm of ALL pyramid levels in two launches, into one token buffer (include/tf_fused.h tf_groupnorm_levels_nhwc_f32): the
+// input projections of a frame (models/deformable_detr.py:73-90 of the reference, then the flatten + concatenation of
+// models/deformable_transformer.py:139-156).  Per level the chain was GEMM [-> split-K reduce] -> zero -> statistics -> apply, then one
+// concatenation of the normalised levels: 16 launches at four levels, 13 of which only hand data to the next one.  Here:
+//   groupnorm_levels_stats_kernel   a workgroup per (level, row block, image).  A level whose source is still the split-K partial sums
+//                                   of its GEMM forms y = ((p0 + p1) + ...) + bias first, in the order of stream_splitk_reduce_kernel
+//                                   (bit-identical y), and stores it at the level's rows of the output.  Every element is widened to
+//                                   double before it is squared and summed (groupnorm_stats_kernel says why).  The workgroup's 2 G sums are
+//                                   added in a FIXED order (no atomics, LDS or global) and go to the workgroup's own slot of the workspace:
+//                                   every slot is written, nothing is cleared, the result is bitwise reproducible.
+//   groupnorm_levels_apply_kernel   a workgroup per (level, 64 rows, image): adds the slots of its (level, image) in a fixed order (256 / G
+//                                   threads per group, each a strided chain; then the chains in order), forms mean / rstd as
+//                                   groupnorm_apply_kernel does and writes (y - mean) rstd gamma + beta to the output rows -- in place
+//                                   over the y of the first pass, or from the level's source.
+// Both kernels keep every floating-point operation as written (no contraction): tests restate them operation by operation.
+constexpr int kGnMaxLevels = 8;
+constexpr int kGnApplyRows = 64;
+
+struct GnLevel {
+    const float *src;            // pieces == 1: y [N, HW, C]; else the partial sums [pieces][N * HW * C]
+    const float *bias;           // pieces > 1: added behind the partial sums (NULL: none)
+    const float *gamma, *beta;
+    long long row0;              // the level's first row of an image of the output
+    int pieces, HW;
+    int rows_per_block;          // statistics pass
+    int sblock0, sblocks;        // its first workgroup (= workspace slot) and their number
+    int ablock0;                 // first workgroup of the normalising pass
+};
+
+struct GnLevels {
+    GnLevel l[kGnMaxLevels];
+    int n;
+};
+
+typedef double f64x2_t __attribute__((ext_vector_type(2)));
+
+// rows a statistics workgroup owns: 64 (groupnorm_stats_kernel's); fewer where every element costs `pieces` loads, so that a level
+// of few rows under many pieces (273 rows x 58 at 800 x 1333) still spreads over as many workgroups as its reduce launch had waves
+int gn_levels_rows_per_block(int pieces, int C)
+{
+    if (pieces <= 1) return kGnRowsPerBlock;
+    const int nslots = 256 / (C / 4);
+    const int rows = (kGnRowsPerBlock / (pieces > kGnRowsPerBlock ? kGnRowsPerBlock : pieces)) / nslots * nslots;
+    return rows < nslots ? nslots : rows;
+}
+
+__global__ void __launch_bounds__(256)
+groupnorm_levels_stats_kernel(const GnLevels lv, float *out, double *__restrict__ ws, int N, int C, int G, long long out_image_stride,
+                              int total_sblocks)
+{
+#pragma clang fp contract(off)
+    __shared__ double s_part[2][4][256];   // [sum | sum of squares][channel of the quad][thread]
+    int li = 0;
+#pragma unroll
+    for (int i = 1; i < kGnMaxLevels; ++i)
+        if (i < lv.n && (int)blockIdx.x >= lv.l[i].sblock0) li = i;
+    const GnLevel &L = lv.l[li];
+    const int C4 = C >> 2, cpg = C / G;
+    const int n = blockIdx.y;
+    const int HW = L.HW, pieces = L.pieces;
+    const int r0 = ((int)blockIdx.x - L.sblock0) * L.rows_per_block, r1 = min(HW, r0 + L.rows_per_block);
+    const int nslots = 256 / C4;   // >= 1 (host: C <= 1024)
+    const int q = threadIdx.x % C4, rslot = threadIdx.x / C4;
+    if (rslot < nslots) {
+        double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0, q0 = 0.0, q1 = 0.0, q2 = 0.0, q3 = 0.0;
+        auto acc = [&](const f32x4_t &v) {
+            const double a = (double)v.x, b = (double)v.y, c = (double)v.z, d = (double)v.w;
+            s0 += a; s1 += b; s2 += c; s3 += d;
+            q0 = fma(a, a, q0); q1 = fma(b, b, q1); q2 = fma(c, c, q2); q3 = fma(d, d, q3);   // (a a is exact in double)
+        };
+        int r = r0 + rslot;
+        if (pieces == 1) {
+            const f32x4_t *xp = reinterpret_cast<const f32x4_t *>(L.src + (long long)n * HW * C);
+            for (; r + 3 * nslots < r1; r += 4 * nslots) {   // four rows in flight per thread, accumulated in row order
+                const f32x4_t v0 = xp[(long long)r * C4 + q], v1 = xp[(long long)(r + nslots) * C4 + q];
+                const f32x4_t v2 = xp[(long long)(r + 2 * nslots) * C4 + q], v3 = xp[(long long)(r + 3 * nslots) * C4 + q];
+                acc(v0);
+                acc(v1);
+                acc(v2);
+                acc(v3);
+            }
+            for (; r < r1; r += nslots) acc(xp[(long long)r * C4 + q]);
+        } else {
+            const long long mn4 = (long long)N * HW * C4;   // one piece, in quads
+            const f32x4_t *pp = reinterpret_cast<const f32x4_t *>(L.src) + (long long)n * HW * C4;
+            f32x4_t *yp = reinterpret_cast<f32x4_t *>(out + (long long)n * out_image_stride + L.row0 * C);
+            f32x4_t bq = {0.f, 0.f, 0.f, 0.f};
+            if (L.bias != nullptr) bq = reinterpret_cast<const f32x4_t *>(L.bias)[q];
+            for (; r < r1; r += nslots) {
+                const f32x4_t *p = pp + (long long)r * C4 + q;
+                f32x4_t y = p[0];
+                int z = 1;
+                for (; z + 3 < pieces; z += 4) {   // stream_splitk_reduce_kernel's loop: four loads in flight, added in the order z, z + 1, ...
+                    const f32x4_t a = p[(long long)z * mn4], b = p[(long long)(z + 1) * mn4], c = p[(long long)(z + 2) * mn4], d = p[(long long)(z + 3) * mn4];
+                    y += a;
+                    y += b;
+                    y += c;
+                    y += d;
+                }
+                for (; z < pieces; ++z) y += p[(long long)z * mn4];
+                if (L.bias != nullptr) y += bq;
+                yp[(long long)r * C4 + q] = y;   // (read again by the normalising pass: an ordinary store)
+                acc(y);
+            }
+        }
+        s_part[0][0][threadIdx.x] = s0; s_part[0][1][threadIdx.x] = s1; s_part[0][2][threadIdx.x] = s2; s_part[0][3][threadIdx.x] = s3;
+        s_part[1][0][threadIdx.x] = q0; s_part[1][1][threadIdx.x] = q1; s_part[1][2][threadIdx.x] = q2; s_part[1][3][threadIdx.x] = q3;
+    }
+    __syncthreads();
+    // group g, statistic st: the threads' sums in the order row slot 0, 1, ..., inside a slot the group's channels ascending
+    double *slot = ws + ((long long)n * total_sblocks + blockIdx.x) * 2 * G;
+    for (int i = threadIdx.x; i < 2 * G; i += blockDim.x) {
+        const int g = i >> 1, st = i & 1;
+        double a = 0.0;
+        for (int rs = 0; rs < nslots; ++rs)
+            for (int c = g * cpg; c < (g + 1) * cpg; ++c) a += s_part[st][c & 3][rs * C4 + (c >> 2)];
+        slot[i] = a;
+    }
+}
+
+__global__ void __launch_bounds__(256)
+groupnorm_levels_apply_kernel(const GnLevels lv, float *out, const double *__restrict__ ws, int N, int C, int G, float eps,
+                              long long out_image_stride, int total_sblocks)
+{
+#pragma clang fp contract(off)
+    __shared__ f64x2_t s_red[256];
+    __shared__ float s_mean[256], s_rstd[256];
+    int li = 0;
+#pragma unroll
+    for (int i = 1; i < kGnMaxLevels; ++i)
+        if (i < lv.n && (int)blockIdx.x >= lv.l[i].ablock0) li = i;
+    const GnLevel &L = lv.l[li];
+    const int C4 = C >> 2, cpg = C / G;
+    const int n = blockIdx.y;
+    const int HW = L.HW;
+    // (sum, sum of squares) of group g over the level's slots: chain p of P = 256 / G adds the slots p, p + P, ... in that order, thread
+    // g then the chains 0, 1, ...
+    {
+        const int P = 256 / G;   // >= 1 (host: G <= 256)
+        const int g = threadIdx.x % G, p = threadIdx.x / G;
+        if (p < P) {
+            const f64x2_t *sp = reinterpret_cast<const f64x2_t *>(ws) + ((long long)n * total_sblocks + L.sblock0) * G + g;
+            f64x2_t a = {0.0, 0.0};
+            int s = p;
+            for (; s + 3 * P < L.sblocks; s += 4 * P) {   // four loads in flight
+                const f64x2_t v0 = sp[(long long)s * G], v1 = sp[(long long)(s + P) * G], v2 = sp[(long long)(s + 2 * P) * G],
+                              v3 = sp[(long long)(s + 3 * P) * G];
+                a += v0;
+                a += v1;
+                a += v2;
+                a += v3;
+            }
+            for (; s < L.sblocks; s += P) a += sp[(long long)s * G];
+            s_red[p * G + g] = a;
+        }
+        __syncthreads();
+        if ((int)threadIdx.x < G) {
+            f64x2_t t = s_red[threadIdx.x];
+            for (int k = 1; k < P; ++k) t += s_red[k * G + threadIdx.x];
+            // groupnorm_apply_kernel's statistics
+            const double cnt = (double)HW * (double)cpg;
+            const double mean = t.x / cnt;
+            double var = t.y / cnt - mean * mean;   // biased, as torch.nn.GroupNorm
+            if (var < 0.0) var = 0.0;
+            s_mean[threadIdx.x] = (float)mean;
+            s_rstd[threadIdx.x] = (float)(1.0 / sqrt(var + (double)eps));
+        }
+        __syncthreads();
+    }
+    const int r0 = ((int)blockIdx.x - L.ablock0) * kGnApplyRows, r1 = min(HW, r0 + kGnApplyRows);
+    f32x4_t *op = reinterpret_cast<f32x4_t *>(out + (long long)n * out_image_stride + (L.row0 + r0) * C);
+    // a level that arrived as partial sums: its y stands at the output rows (in place: a thread reads what it alone overwrites)
+    const f32x4_t *xp = L.pieces > 1 ? op : reinterpret_cast<const f32x4_t *>(L.src + ((long long)n * HW + r0) * C);
+    const int n4 = (r1 - r0) * C4;
+    auto norm = [&](const f32x4_t &v, int q) {
+        const int g0 = (q * 4) / cpg, g1 = (q * 4 + 1) / cpg, g2 = (q * 4 + 2) / cpg, g3 = (q * 4 + 3) / cpg;
+        const f32x4_t ga = reinterpret_cast<const f32x4_t *>(L.gamma)[q], be = reinterpret_cast<const f32x4_t *>(L.beta)[q];
+        f32x4_t y;
+        y.x = (v.x - s_mean[g0]) * s_rstd[g0] * ga.x + be.x;
+        y.y = (v.y - s_mean[g1]) * s_rstd[g1] * ga.y + be.y;
+        y.z = (v.z - s_mean[g2]) * s_rstd[g2] * ga.z + be.z;
+        y.w = (v.w - s_mean[g3]) * s_rstd[g3] * ga.w + be.w;
+        return y;
+    };
+    int i = threadIdx.x;
+    for (; i + 768 < n4; i += 1024) {   // four quads in flight per thread
+        const f32x4_t v0 = xp[i], v1 = xp[i + 256], v2 = xp[i + 512], v3 = xp[i + 768];
+        tfm::stream_store(op + i, norm(v0, i % C4));
+        tfm::stream_store(op + i + 256, norm(v1, (i + 256) % C4));
+        tfm::stream_store(op + i + 512, norm(v2, (i + 512) % C4));
+        tfm::stream_store(op + i + 768, norm(v3, (i + 768) % C4));
+    }
+    for (; i < n4; i += 256) tfm::stream_store(op + i, norm(xp[i], i % C4));
+}
+
 // ---- the FPN merge of the mask head (include/tf_fused.h tf_upsample_add_nhwc_f32): one thread per (output pixel, 4 channels)
 __global__ void __launch_bounds__(256)
 upsample_add_nhwc_kernel(const float *__restrict__ low, const float *__restrict__ fpn, float *__restrict__ out, int q_per_image,
@@ -670,6 +865,70 @@ int tf_groupnorm_relu_nhwc_f32(const float *x, const float *gamma, const float *
                                int HW, int C, int G, float eps, int64_t x_image_stride, int64_t out_image_stride, void *stream)
 {
     return groupnorm_nhwc_impl(x, gamma, beta, out, workspace, N, HW, C, G, eps, x_image_stride, out_image_stride, true, stream);
+}
+
+// validates the table and lays the two grids out; TF_MSDA_OK and *total_sblocks = workgroups (= workspace slots per image) of the
+// statistics pass, *total_ablocks = those of the normalising pass
+static int gn_levels_plan(const tf_gn_level *levels, int nlevels, int N, int C, int G, GnLevels *lv, long long *total_sblocks,
+                          long long *total_ablocks)
+{
+    if (!levels) return TF_MSDA_ERR_NULL_POINTER;
+    if (nlevels < 1 || nlevels > kGnMaxLevels) return TF_MSDA_ERR_BAD_DIMS;
+    for (int i = 0; i < nlevels; ++i)
+        if (!levels[i].src || !levels[i].gamma || !levels[i].beta) return TF_MSDA_ERR_NULL_POINTER;
+    if (N <= 0 || N > 65535 || C <= 0 || G <= 0 || G > 256 || C > 1024 || (C % G) != 0 || (C & 3)) return TF_MSDA_ERR_BAD_DIMS;
+    long long sb = 0, ab = 0;
+    lv->n = nlevels;
+    for (int i = 0; i < nlevels; ++i) {
+        const tf_gn_level &t = levels[i];
+        if (t.HW <= 0 || t.pieces < 1 || t.pieces > 65535 || t.row0 < 0 || (long long)N * t.HW * (C / 4) >= (1LL << 31)) return TF_MSDA_ERR_BAD_DIMS;
+        if (!aligned16(t.src) || !aligned16(t.gamma) || !aligned16(t.beta) || (t.bias && !aligned16(t.bias))) return TF_MSDA_ERR_BAD_DIMS;
+        for (int j = 0; j < i; ++j)   // the levels' rows of the output must not overlap
+            if (t.row0 < levels[j].row0 + levels[j].HW && levels[j].row0 < t.row0 + t.HW) return TF_MSDA_ERR_BAD_DIMS;
+        GnLevel &l = lv->l[i];
+        l = GnLevel{t.src, t.pieces > 1 ? t.bias : nullptr, t.gamma, t.beta, (long long)t.row0, t.pieces, t.HW, gn_levels_rows_per_block(t.pieces, C),
+                    (int)sb, 0, (int)ab};
+        l.sblocks = (t.HW + l.rows_per_block - 1) / l.rows_per_block;
+        sb += l.sblocks;
+        ab += (t.HW + kGnApplyRows - 1) / kGnApplyRows;
+        if (sb > 0x3fffffffLL) return TF_MSDA_ERR_BAD_DIMS;
+    }
+    *total_sblocks = sb;
+    *total_ablocks = ab;
+    return TF_MSDA_OK;
+}
+
+int64_t tf_groupnorm_levels_workspace_doubles(const tf_gn_level *levels, int nlevels, int N, int C, int G)
+{
+    GnLevels lv{};
+    long long sb = 0, ab = 0;
+    if (gn_levels_plan(levels, nlevels, N, C, G, &lv, &sb, &ab) != TF_MSDA_OK) return -1;
+    return (int64_t)N * sb * 2 * G;
+}
+
+int tf_groupnorm_levels_nhwc_f32(const tf_gn_level *levels, int nlevels, int N, int C, int G, float eps, float *out,
+                                 int64_t out_image_stride, double *workspace, void *stream)
+{
+    if (!levels || !out || !workspace) return TF_MSDA_ERR_NULL_POINTER;
+    GnLevels lv{};
+    long long sb = 0, ab = 0;
+    const int rc = gn_levels_plan(levels, nlevels, N, C, G, &lv, &sb, &ab);
+    if (rc != TF_MSDA_OK) return rc;
+    if (!aligned16(out) || !aligned16(workspace) || out_image_stride <= 0 || (out_image_stride & 3)) return TF_MSDA_ERR_BAD_DIMS;
+    for (int i = 0; i < nlevels; ++i) {
+        if ((levels[i].row0 + levels[i].HW) * (int64_t)C > out_image_stride) return TF_MSDA_ERR_BAD_DIMS;
+        // a level normalised from its source must not be (part of) the output: other workgroups write there
+        const uintptr_t a = reinterpret_cast<uintptr_t>(levels[i].src), b = a + (uintptr_t)N * levels[i].HW * C * levels[i].pieces * 4;
+        const uintptr_t o = reinterpret_cast<uintptr_t>(out);
+        if (a < o + (uintptr_t)N * out_image_stride * 4 && o < b) return TF_MSDA_ERR_BAD_DIMS;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(groupnorm_levels_stats_kernel, dim3((unsigned)sb, (unsigned)N), dim3(256), 0, s, lv, out, workspace, N, C, G,
+                       (long long)out_image_stride, (int)sb);
+    if (hipGetLastError() != hipSuccess) return TF_MSDA_ERR_LAUNCH;
+    hipLaunchKernelGGL(groupnorm_levels_apply_kernel, dim3((unsigned)ab, (unsigned)N), dim3(256), 0, s, lv, out, (const double *)workspace, N,
+                       C, G, eps, (long long)out_image_stride, (int)sb);
+    return hipGetLastError() == hipSuccess ? TF_MSDA_OK : TF_MSDA_ERR_LAUNCH;
 }
 
 int tf_bias_act_f32(float *x, const float *bias, const float *residual, int64_t n, int C, int relu,

@@ -966,6 +966,8 @@ struct StreamCall {
     StreamConv cv;
     float *workspace;   // split-K partial sums [pieces][M][N], or NULL
     int ksplit;         // pieces the K loop is cut into (1: none)
+    int *deferred = nullptr;   // deferred reduce: the partial sums stay in `workspace` for the consumer and *deferred = their number
+                               // (1: the launch was not split -- the caller passes y == workspace, which then holds the finished y)
 };
 
 // the second pass of a split sum: out [count] = [relu](sum of the `pieces` partials [pieces][count] + bias + res), rows of `cols` floats
@@ -998,6 +1000,10 @@ int launch_stream(const StreamCall &c, hipStream_t s)
                        (partial && !XSC) ? nullptr : c.bias, partial ? nullptr : c.res, out, c.M, c.K, c.N, mblocks, nblocks, partial ? 0 : c.relu,
                        kslices, c.cv);   // (XSC: `bias` is scale2 -- every partial sum is staged with s and leaves with 1 / s)
     if (hipGetLastError() != hipSuccess) return TF_MSDA_ERR_LAUNCH;
+    if (c.deferred != nullptr) {
+        *c.deferred = gz;
+        return TF_MSDA_OK;
+    }
     return partial ? launch_splitk_reduce(c.workspace, XSC ? nullptr : c.bias, c.res, c.y, (long long)c.M * c.N, c.N, gz, c.relu, s) : TF_MSDA_OK;
 }
 
@@ -1060,6 +1066,10 @@ int launch_halo(const StreamCall &c, hipStream_t s, const HaloMerge mg = HaloMer
                        (partial && !XSC) ? nullptr : c.bias, partial ? nullptr : c.res, out, c.N, nblocks, (int)npatches, tiles_x, tiles_y,
                        partial ? 0 : c.relu, cslices, c.cv, mg);   // (XSC: as launch_stream)
     if (hipGetLastError() != hipSuccess) return TF_MSDA_ERR_LAUNCH;
+    if (c.deferred != nullptr) {
+        *c.deferred = gz;
+        return TF_MSDA_OK;
+    }
     return partial ? launch_splitk_reduce(c.workspace, XSC ? nullptr : c.bias, c.res, c.y, (long long)c.M * c.N, c.N, gz, c.relu, s) : TF_MSDA_OK;
 }
 
@@ -1212,9 +1222,9 @@ extern "C" int tf_linear_packed_f32(const float *x, const void *w_packed, const 
     return stream_dispatch_scheme<false>(sp, c, static_cast<hipStream_t>(stream));
 }
 
-extern "C" int tf_conv_packed_f32(const float *x, const void *w_packed, const float *bias, const float *residual, float *y,
-                                  float *workspace, int ksplit, int nimg, int hin, int win, int cin, int cout, int ks, int stride,
-                                  int relu, int terms, void *stream)
+static int conv_packed_impl(const float *x, const void *w_packed, const float *bias, const float *residual, float *y, float *workspace,
+                            int ksplit, int nimg, int hin, int win, int cin, int cout, int ks, int stride, int relu, int terms,
+                            int *deferred, void *stream)
 {
     if (!x || !w_packed || !y) return TF_MSDA_ERR_NULL_POINTER;
     const int sp = split_scheme(terms);
@@ -1236,10 +1246,26 @@ extern "C" int tf_conv_packed_f32(const float *x, const void *w_packed, const fl
         al |= reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(bias) | reinterpret_cast<uintptr_t>(residual);
     }
     if (al & 15) return TF_MSDA_ERR_BAD_DIMS;
-    StreamCall c{x, static_cast<const u32x4 *>(w_packed), bias, residual, y, (int)M, ks * ks * cin, cout, relu, true, cv, workspace, ksplit};
+    StreamCall c{x, static_cast<const u32x4 *>(w_packed), bias, residual, y, (int)M, ks * ks * cin, cout, relu, true, cv, workspace, ksplit, deferred};
     if (halo)   // the halo form: every input pixel staged once per channel slice, not once per tap
         return sp == 3 ? halo_dispatch<3>(c, static_cast<hipStream_t>(stream)) : halo_dispatch<16>(c, static_cast<hipStream_t>(stream));
     return stream_dispatch_scheme<true>(sp, c, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int tf_conv_packed_f32(const float *x, const void *w_packed, const float *bias, const float *residual, float *y,
+                                  float *workspace, int ksplit, int nimg, int hin, int win, int cin, int cout, int ks, int stride,
+                                  int relu, int terms, void *stream)
+{
+    return conv_packed_impl(x, w_packed, bias, residual, y, workspace, ksplit, nimg, hin, win, cin, cout, ks, stride, relu, terms, nullptr, stream);
+}
+
+extern "C" int tf_conv_packed_partials_f32(const float *x, const void *w_packed, const float *bias, float *workspace, int ksplit, int nimg,
+                                           int hin, int win, int cin, int cout, int ks, int stride, int terms, int *pieces, void *stream)
+{
+    if (!workspace || !pieces) return TF_MSDA_ERR_NULL_POINTER;
+    // every check of the split form, whatever ksplit (an unsplit launch writes y = workspace)
+    if ((cout & 3) || ((reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(bias)) & 15)) return TF_MSDA_ERR_BAD_DIMS;
+    return conv_packed_impl(x, w_packed, bias, nullptr, workspace, workspace, ksplit, nimg, hin, win, cin, cout, ks, stride, 0, terms, pieces, stream);
 }
 
 // the backward of a linear (statistics, weight gradient, input gradient): kernels and entry points

@@ -104,6 +104,24 @@ class DeformableDETR(DETR):
                 return y
         return proj(x)
 
+    def _input_proj_all_levels(self, frames):
+        """The input projections of every level of every frame through fused.input_proj_levels (one GroupNorm call for all of them,
+        written into one token buffer) -> the src_list of encode_frame, or None: inference on the GPU only, not with
+        merge_frame_features (those models concatenate per level before a further convolution), at most one extra level (a second
+        one reads the first's output)."""
+        if (self.training or torch.is_grad_enabled() or self.merge_frame_features
+                or self.num_feature_levels > len(frames[0]) + 1 or not fused.input_proj_levels_enabled()):
+            return None
+        items = []
+        for frame_feat in frames:
+            xs = [feat.tensors for feat in frame_feat]
+            if self.num_feature_levels > len(frame_feat):
+                xs.append(frame_feat[-1].tensors)   # the extra level: a 3 x 3 / stride 2 convolution of the coarsest feature map
+            if len(xs) != self.num_feature_levels or not all(x.is_cuda for x in xs):
+                return None
+            items.extend((x, self.input_proj[lvl][0], self.input_proj[lvl][1]) for lvl, x in enumerate(xs))
+        return fused.input_proj_levels(items)
+
     def _project(self, level, x, prev_x=None):
         y = self._input_proj(level, x)
         if self.merge_frame_features:
@@ -141,6 +159,7 @@ class DeformableDETR(DETR):
         prev_features = features if prev_features is None else prev_features[-3:]
 
         frames = [prev_features, features] if self.multi_frame_attention else [features]
+        projected = self._input_proj_all_levels(frames)   # every level of every frame at once (None: level by level below)
         src_list, mask_list, pos_list = [], [], []
         for frame, frame_feat in enumerate(frames):
             per_frame_pos = self.multi_frame_attention and self.multi_frame_encoding
@@ -149,11 +168,13 @@ class DeformableDETR(DETR):
                 src, mask = feat.decompose()
                 assert mask is not None
                 prev_src = prev_features[lvl].tensors if self.merge_frame_features else None
-                src_list.append(self._project(lvl, src, prev_src))
+                src_list.append(projected[len(src_list)] if projected is not None else self._project(lvl, src, prev_src))
                 mask_list.append(mask)
 
             for lvl in range(len(frame_feat), self.num_feature_levels):  # extra coarse levels
-                if lvl == len(frame_feat):
+                if projected is not None:
+                    src = projected[len(src_list)]
+                elif lvl == len(frame_feat):
                     src = self._project(lvl, frame_feat[-1].tensors,
                                         prev_features[-1].tensors if self.merge_frame_features
                                         else None)

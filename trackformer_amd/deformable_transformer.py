@@ -116,6 +116,28 @@ _GEOMETRY = _GeometryCache()
 _KEEP_CACHE_ENTRIES = 64
 
 
+def _token_buffer_of(srcs):
+    """The [N, S, C] token buffer the levels `srcs` ([N, C, H_l, W_l] each) already stand in, one behind the other -- what
+    torch.cat([s.flatten(2).transpose(1, 2) for s in srcs], 1) would copy them into -- as a view, or None.  Recognised by what the
+    tensors ARE (one storage, channels-innermost strides with the buffer's image stride, consecutive offsets), never by a flag."""
+    s0 = srcs[0]
+    n, c = s0.shape[0], s0.shape[1]
+    total = sum(int(s.shape[2]) * int(s.shape[3]) for s in srcs)
+    store, offset = s0.untyped_storage().data_ptr(), s0.storage_offset()
+    first = offset
+    for s in srcs:
+        h, w = int(s.shape[2]), int(s.shape[3])
+        if not (s.dim() == 4 and s.shape[0] == n and s.shape[1] == c and s.dtype == s0.dtype and s.device == s0.device
+                and s.untyped_storage().data_ptr() == store and s.storage_offset() == offset
+                and (n == 1 or s.stride(0) == total * c) and s.stride(1) == 1
+                and (h == 1 or s.stride(2) == w * c) and (w == 1 or s.stride(3) == c)):
+            return None
+        offset += h * w * c
+    if (first + (n - 1) * total * c + total * c) * s0.element_size() > s0.untyped_storage().nbytes():
+        return None
+    return torch.as_strided(s0, (n, total, c), (total * c, c, 1), first)
+
+
 def _host_shapes(spatial_shapes):
     """(H, W) python ints of a spatial_shapes tensor (attached by DeformableTransformer.forward;
     falls back to one device read for foreign callers)."""
@@ -273,7 +295,9 @@ class DeformableTransformer(nn.Module):
         still associates frame t: the track queries enter in decode()."""
         shapes = tuple((int(s.shape[2]), int(s.shape[3])) for s in srcs)
         device = srcs[0].device
-        src_flatten = torch.cat([s.flatten(2).transpose(1, 2) for s in srcs], 1)
+        src_flatten = _token_buffer_of(srcs)   # the levels already stand in one [N, S, C] buffer (fused.input_proj_levels)
+        if src_flatten is None:
+            src_flatten = torch.cat([s.flatten(2).transpose(1, 2) for s in srcs], 1)
         lvl_pos_embed_flatten = self._level_position_embedding(pos_embeds)
         unpadded = all(is_all_valid(m) for m in masks)
         if unpadded:

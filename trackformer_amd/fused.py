@@ -4,6 +4,7 @@ The first part serves the inference path (eval mode, gradients disabled) on GPU 
 TRAINING PATH OF ..., DROPOUT INSIDE THE TRAINING KERNELS) are opt-in autograd Functions over the library's own backward kernels, each
 behind a process-wide switch that is off by default.  Everywhere else the callers keep the plain PyTorch formulation (these helpers
 return None when they do not apply)."""
+import ctypes
 import os
 import threading
 
@@ -1112,6 +1113,34 @@ def groupnorm_relu_conv3x3_c1(x, gn, conv):
     return out
 
 
+def _input_proj_taps(conv):
+    """The persistent [Cout, 9 * Cin] tap-major image of the extra level's 3 x 3 weight: the split pieces are cached on it."""
+    cout, cin = conv.out_channels, conv.in_channels
+    hit = getattr(conv, "_tf_wtaps", None)
+    key = source_key(conv.weight)
+    if hit is None or hit[0] != key or hit[2] is not conv.weight:
+        prev_img = None if hit is None else hit[1]
+        hit = (key, conv.weight.detach().permute(0, 2, 3, 1).reshape(cout, 9 * cin).contiguous(), conv.weight)
+        inherit_route(hit[1], conv.weight, prev_img)
+        conv._tf_wtaps = hit
+    return hit[1]
+
+
+def _input_proj_w2d(conv):
+    """The persistent [Cout, Cin] view of a 1 x 1 level's weight: the split pieces are cached on it."""
+    cout, cin = conv.out_channels, conv.in_channels
+    hit = getattr(conv, "_tf_w2d", None)
+    key = source_key(conv.weight)
+    if hit is None or hit[0] != key or hit[2] is not conv.weight:
+        prev_img = None if hit is None else hit[1]
+        hit = (key, conv.weight.detach().reshape(cout, cin).contiguous(), conv.weight)
+        inherit_route(hit[1], conv.weight, prev_img)
+        if hit[1].is_cuda and hit[1].data_ptr() != conv.weight.data_ptr():   # a copy made on this stream: publish for the others
+            _publish_barrier(hit[1].device)
+        conv._tf_w2d = hit
+    return hit[1]
+
+
 def input_proj_1x1(x, conv, gn):
     """GroupNorm(conv(x)) for the input projections -- 1 x 1 convolutions, and the extra level's 3 x 3 / stride 2 one -- of a
     channels_last fp32 GPU activation x [N, Cin, H, W]; returns [N, Cout, H', W']
@@ -1122,15 +1151,8 @@ def input_proj_1x1(x, conv, gn):
         # the extra pyramid level (deformable_detr.py:55-79: Conv2d(2048, hidden, 3, stride 2, padding 1) + GroupNorm)
         if not x.is_contiguous(memory_format=torch.channels_last):
             x = x.contiguous(memory_format=torch.channels_last)
-        cout, cin = conv.out_channels, conv.in_channels
-        hit = getattr(conv, "_tf_wtaps", None)   # persistent [Cout, 9 * Cin] tap-major image: the split pieces are cached on it
-        key = source_key(conv.weight)
-        if hit is None or hit[0] != key or hit[2] is not conv.weight:
-            prev_img = None if hit is None else hit[1]
-            hit = (key, conv.weight.detach().permute(0, 2, 3, 1).reshape(cout, 9 * cin).contiguous(), conv.weight)
-            inherit_route(hit[1], conv.weight, prev_img)
-            conv._tf_wtaps = hit
-        y = conv3x3(x, hit[1], conv.bias, False, 2)
+        cout = conv.out_channels
+        y = conv3x3(x, _input_proj_taps(conv), conv.bias, False, 2)
         if y is None:
             return None
         n, _, ho, wo = y.shape
@@ -1142,27 +1164,173 @@ def input_proj_1x1(x, conv, gn):
         x = x.contiguous(memory_format=torch.channels_last)
     n, cin, h, w = x.shape
     cout = conv.out_channels
-    hit = getattr(conv, "_tf_w2d", None)   # persistent [Cout, Cin] view: the split pieces are cached on it
-    key = source_key(conv.weight)
-    if hit is None or hit[0] != key or hit[2] is not conv.weight:
-        prev_img = None if hit is None else hit[1]
-        hit = (key, conv.weight.detach().reshape(cout, cin).contiguous(), conv.weight)
-        inherit_route(hit[1], conv.weight, prev_img)
-        if hit[1].is_cuda and hit[1].data_ptr() != conv.weight.data_ptr():   # a copy made on this stream: publish for the others
-            _publish_barrier(hit[1].device)
-        conv._tf_w2d = hit
+    w2d = _input_proj_w2d(conv)
     y2 = None
     if conv1x1_wants_split_k(n * h * w, cin, cout):   # the coarse levels: 1050 / 4200 pixels under K = 2048 / 1024
-        y = conv3x3(x, hit[1], conv.bias, False, 1)
+        y = conv3x3(x, w2d, conv.bias, False, 1)
         y2 = None if y is None else y.permute(0, 2, 3, 1)
     if y2 is None:
-        y2 = linear(x.permute(0, 2, 3, 1).reshape(n * h * w, cin), hit[1], conv.bias)
+        y2 = linear(x.permute(0, 2, 3, 1).reshape(n * h * w, cin), w2d, conv.bias)
     if y2 is None:
         return None
     z2 = groupnorm_nhwc(y2.reshape(n * h * w, cout), n, gn)
     if z2 is None:
         return None
     return z2.view(n, h, w, cout).permute(0, 3, 1, 2)
+
+
+# ALL input-projection levels of a frame normalised by ONE tf_groupnorm_levels_nhwc_f32 call (two launches) straight into the
+# encoder's token buffer [N, S, C] (TF_INPUT_PROJ_LEVELS=0 / set_input_proj_levels(False): the per-level route above).  The coarse
+# levels' GEMMs leave their split-K partial sums (tf_conv_packed_partials_f32) and the statistics pass adds them, so per frame the
+# split-K reduce launches behind those levels, four x (zero, statistics, apply) and the concatenation in DeformableTransformer.encode
+# are gone: 16 launches -> 2 at 800 x 1333, and no atomics (bitwise reproducible).  Measurements: profiles/gn_levels_bench.json.
+# From 4096 rows on, as the other fused routes (only the full-size frame was measured).
+_input_proj_levels = os.environ.get("TF_INPUT_PROJ_LEVELS", "1") != "0"
+_INPUT_PROJ_LEVELS_MIN_ROWS = int(os.environ.get("TF_INPUT_PROJ_LEVELS_MIN_ROWS", "4096"))
+
+
+def input_proj_levels_enabled():
+    return _input_proj_levels
+
+
+def set_input_proj_levels(on):
+    """Switch the all-levels GroupNorm route of the input projections on or off (process-wide); returns the previous setting."""
+    global _input_proj_levels
+    prev, _input_proj_levels = _input_proj_levels, bool(on)
+    return _switched(prev, _input_proj_levels)
+
+
+def set_input_proj_levels_min_rows(n):
+    """Rows (summed over images and levels) from which input_proj_levels() applies (process-wide); returns the previous value."""
+    global _INPUT_PROJ_LEVELS_MIN_ROWS
+    prev, _INPUT_PROJ_LEVELS_MIN_ROWS = _INPUT_PROJ_LEVELS_MIN_ROWS, int(n)
+    return _switched(prev, _INPUT_PROJ_LEVELS_MIN_ROWS)
+
+
+def _conv_partials(x, w_taps, bias, stride):
+    """conv3x3()'s stream route (tf_conv_packed_f32) for a shape whose K loop is cut, with the second pass left to the consumer
+    (tf_conv_packed_partials_f32) -> (partials [pieces', M * Cout] fp32, pieces the launch wrote); pieces == 1: the first M * Cout floats
+    are the finished output, bias added.  None where conv3x3() would not take that route with a split: the caller keeps conv3x3()."""
+    if not (_split_linear and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
+            and x.is_contiguous(memory_format=torch.channels_last) and w_taps.dtype == torch.float32
+            and w_taps.dim() == 2 and w_taps.is_contiguous() and w_taps.device == x.device):
+        return None
+    n, cin, h, w = x.shape
+    cout = w_taps.shape[0]
+    ks = 3 if w_taps.shape[1] == 9 * cin else 1
+    if w_taps.shape[1] != ks * ks * cin or cin % 64 or stride not in (1, 2) or x.numel() == 0 or (ks == 3 and stride == 1):
+        return None   # (the stride-1 3 x 3 layers -- the halo form, its own split policy -- are no input projection)
+    if bias is not None and not (_param_ok(bias, x) and bias.numel() == cout):
+        return None
+    pad = 1 if ks == 3 else 0
+    ho, wo = (h + 2 * pad - ks) // stride + 1, (w + 2 * pad - ks) // stride + 1
+    m = n * ho * wo
+    if not (_conv_stream and _conv_stream_wins(m, cout) and not (x.data_ptr() & 15) and n * h * w * cin * 4 < 0xC0000000
+            and (m + 256) * cout * 4 < 0xC0000000):
+        return None
+    ksplit = _conv_ksplit(m, ks * ks * cin, cout)
+    if ksplit <= 1 or (ks == 1 and (ksplit < _CONV1X1_MIN_PIECES or not _conv1x1_splitk)):
+        return None
+    packed = _packed_weight(w_taps, None)
+    if packed is None:
+        return None
+    pieces = ctypes.c_int(0)
+    with torch.cuda.device(x.device):
+        ws = torch.empty((ksplit, m * cout), dtype=torch.float32, device=x.device)
+        rc = _cabi.lib().tf_conv_packed_partials_f32(x.data_ptr(), packed.data_ptr(), _ptr(bias), ws.data_ptr(), ksplit, n, h, w, cin, cout,
+                                                     ks, stride, _terms(), ctypes.byref(pieces), _stream(x.device))
+    _cabi.check(rc, "tf_conv_packed_partials_f32")
+    return ws, pieces.value
+
+
+def _groupnorm_levels(levels, n, total, c, groups, eps, device):
+    """One tf_groupnorm_levels_nhwc_f32 call: levels [(src: y [n, HW, c] or partial sums [pieces', n * HW * c], pieces, bias or None, gn, HW)]
+    normalised into consecutive rows of a fresh [n, total, c] buffer, which is returned (None: the entry would refuse the table)."""
+    table = (_cabi.GnLevel * len(levels))()
+    row0 = 0
+    for d, (src, pieces, bias, gn, hw) in zip(table, levels):
+        d.src, d.bias, d.gamma, d.beta = src.data_ptr(), _ptr(bias) or None, gn.weight.data_ptr(), gn.bias.data_ptr()
+        d.pieces, d.HW, d.row0 = pieces, hw, row0
+        row0 += hw
+    L = _cabi.lib()
+    n_ws = L.tf_groupnorm_levels_workspace_doubles(table, len(levels), n, c, groups)
+    if n_ws <= 0:
+        return None
+    with torch.cuda.device(device):
+        out = torch.empty((n, total, c), dtype=torch.float32, device=device)
+        ws = torch.empty(n_ws, dtype=torch.float64, device=device)
+        rc = L.tf_groupnorm_levels_nhwc_f32(table, len(levels), n, c, groups, eps, out.data_ptr(), total * c, ws.data_ptr(), _stream(device))
+    _cabi.check(rc, "tf_groupnorm_levels_nhwc_f32")
+    return out
+
+
+def input_proj_levels(items):
+    """GroupNorm(conv(x)) of ALL input-projection levels of a frame -- items: [(x [N, Cin, H, W], conv, gn)] in token order, the
+    levels input_proj_1x1() takes -- through the level GEMMs (the coarse ones leaving their split-K partial sums) and ONE
+    tf_groupnorm_levels_nhwc_f32 call into a fresh token buffer [N, S, C].  Returns the per-level [N, C, H', W'] views of that buffer
+    (channels_last strides; consecutive: DeformableTransformer.encode uses the buffer itself), or None when it does not apply --
+    switched off, gradients, fewer rows than the threshold, or any level the per-level route would decline: the caller keeps that route."""
+    if not (_input_proj_levels and _input_proj_fused and _split_linear and 1 <= len(items) <= 8) or torch.is_grad_enabled():
+        return None
+    if _split_terms == 16 and (_n_six_term_routes or debug_checks_active()):
+        return None   # per-layer six-term routes, the range audit and the finite check live on the per-layer wrappers
+    x0, _conv0, gn0 = items[0]
+    if not (x0.is_cuda and x0.dim() == 4):
+        return None
+    n, c, groups, eps = x0.shape[0], gn0.num_channels, gn0.num_groups, float(gn0.eps)
+    if c % 4 or c > 1024 or groups > 256 or n > 65535:
+        return None
+    geom = []
+    for x, conv, gn in items:
+        if not (x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and x.device == x0.device and x.shape[0] == n and x.numel()
+                and conv.groups == 1 and conv.in_channels == x.shape[1] and conv.out_channels == c and conv.weight.device == x.device
+                and conv.weight.dtype == torch.float32
+                and gn.num_channels == c and gn.num_groups == groups and float(gn.eps) == eps and gn.weight is not None
+                and gn.bias is not None and _param_ok(gn.weight, x) and _param_ok(gn.bias, x)):
+            return None
+        h, w = x.shape[-2:]
+        if conv.kernel_size == (3, 3) and conv.stride == (2, 2) and conv.padding == (1, 1) and conv.dilation == (1, 1):
+            geom.append((3, (h - 1) // 2 + 1, (w - 1) // 2 + 1))
+        elif conv.kernel_size == (1, 1) and conv.stride == (1, 1) and conv.padding == (0, 0):
+            geom.append((1, h, w))
+        else:
+            return None
+    total = sum(ho * wo for _ks, ho, wo in geom)
+    if n * total < _INPUT_PROJ_LEVELS_MIN_ROWS:
+        return None
+    srcs = []   # (tensor that holds y or the partial sums, pieces, bias)
+    for (x, conv, _gn), (ks, ho, wo) in zip(items, geom):
+        if not x.is_contiguous(memory_format=torch.channels_last):
+            x = x.contiguous(memory_format=torch.channels_last)
+        if ks == 3:
+            wimg = _input_proj_taps(conv)
+            part = _conv_partials(x, wimg, conv.bias, 2)
+            if part is None:
+                y = conv3x3(x, wimg, conv.bias, False, 2)
+                part = None if y is None else (y.permute(0, 2, 3, 1), 1)
+        else:
+            wimg = _input_proj_w2d(conv)
+            part = None
+            if conv1x1_wants_split_k(n * ho * wo, x.shape[1], c):   # the coarse levels: 1050 / 4200 pixels under K = 2048 / 1024
+                part = _conv_partials(x, wimg, conv.bias, 1)
+                if part is None:
+                    y = conv3x3(x, wimg, conv.bias, False, 1)
+                    part = None if y is None else (y.permute(0, 2, 3, 1), 1)
+            if part is None:
+                y2 = linear(x.permute(0, 2, 3, 1).reshape(n * ho * wo, x.shape[1]), wimg, conv.bias)
+                part = None if y2 is None else (y2, 1)
+        if part is None or not part[0].is_contiguous() or (part[0].data_ptr() & 15):
+            return None
+        srcs.append((part[0], part[1], conv.bias if part[1] > 1 else None))
+    out = _groupnorm_levels([(src, pieces, bias, gn, ho * wo) for (src, pieces, bias), (_x, _conv, gn), (_ks, ho, wo) in zip(srcs, items, geom)],
+                            n, total, c, groups, eps, x0.device)
+    if out is None:
+        return None
+    views, row0 = [], 0
+    for _ks, ho, wo in geom:
+        views.append(out[:, row0:row0 + ho * wo].view(n, ho, wo, c).permute(0, 3, 1, 2))   # NCHW shape over the level's rows = channels_last strides
+        row0 += ho * wo
+    return views
 
 
 # DEFAULT since round 3 (TF_BOX_REFINE_FUSED=0 / set_box_refine_fused(False) switches it off; +5.1 % frames/s on its own):
