@@ -683,6 +683,48 @@ int tf_mha_core_f32(const float *q, const float *k, const float *v, float *out, 
                     void *stream);
 
 /*
+ * TRAINING THROUGH THE ATTENTION CORE  (trackformer_amd/csrc/mha_bwd.h and the TRAIN instantiation of the default kernel of
+ * tf_mha_core_f32; reference: the autograd of nn.MultiheadAttention's softmax(q k^T scale) -> dropout -> . v, fp32).  Layouts, key_mask
+ * and scale as tf_mha_core_f32.  With s_ij = q_i . k_j, c = scale log2(e) (the float product scale * 1.44269504088896340736f) and the
+ * keys j the mask leaves:
+ *     stats[n, h, i, 0] = m_i   = max_j fl(c s_ij)                 (the row maximum in units of log2; 0 for a row without keys)
+ *     stats[n, h, i, 1] = inv_i = 1 / sum_j 2^(fl(c s_ij) - m_i)   (the reciprocal row sum; 0 for a row without keys)
+ *     P_ij = 2^(c s_ij - m_i) inv_i  (0 for a masked key),   Pd_ij = keep_ij s_p P_ij,   out_i = sum_j Pd_ij v_j
+ * stats is [N, H, Lq, 2] fp32, contiguous.  Nothing of size Lq x Lk is stored: the backward rebuilds P from q, k and stats.
+ *
+ * THE MASK CONTRACT.  THE GENERATOR CONTRACT (above) applied to the weights as a tensor [N, H, Lq, Lk4] with rows PADDED to
+ * Lk4 = 4 ceil(Lk / 4) keys: the decision for weight (n, h, i, j) is that of flat element r Lk4 + j of the stream `rng`,
+ * r = (n H + h) Lq + i.  A Philox group is therefore always four consecutive keys of one row, whatever Lk is (track queries make it
+ * arbitrary).  tf_dropout_keep_u8 over N H Lq Lk4 elements, viewed as [N, H, Lq, Lk4] and sliced to [..., :Lk], IS the mask.  Masked
+ * keys consume their positions: the decision does not depend on key_mask.  s_p = 1.0f / (1.0f - p) as a float; a dropped weight is
+ * exactly 0 (a select).  rng == NULL: no dropout (keep = 1, s_p = 1; p is not read).
+ *
+ *   tf_mha_core_train_f32   one launch: the default kernel of tf_mha_core_f32 (option mha_mfma = 1, whatever the option holds), which
+ *                           also writes stats and, with rng, drops the weights where P V reads them.  With rng == NULL `out` is
+ *                           bit-identical to tf_mha_core_f32 under mha_mfma = 1.  A row whose keys are all masked gives exactly 0.
+ *   tf_mha_core_bwd_f32     one launch, no workspace:   dP = dout V^T,   delta_i = sum_c dout_ic out_ic (= sum_j Pd_ij dP_ij),
+ *                               dS = P (keep s_p dP - delta),   dq = scale dS K,   dk = scale dS^T Q,   dv = Pd^T dout.
+ *                           Workgroups that own 16 queries walk the keys and write dq; workgroups that own 16 keys walk the queries and
+ *                           write dk and dv; each recomputes delta.  All products are exact-fp32 matrix instructions.  dq / dk / dv
+ *                           have leading dimensions of their own: dq and dk may be the halves of ONE [N, L, 2 E] gradient of a shared
+ *                           q | k projection.  No atomics, LDS included; every element is written once and every sum runs in an order
+ *                           that is a function of (Lq, Lk) alone: bit-identical from call to call, on any stream, in a captured HIP
+ *                           graph and next to concurrent work.
+ * Dead elements are selected, not multiplied: masked keys get dk = dv = +0, rows whose keys are all masked get dq = +0 and their dout
+ * (NaN included) reaches no output.
+ * D in {32, 36}; Lq and Lk in 1 .. 1024, independent; every ld % 4 == 0 and >= H D; tensors 16-byte aligned, stats and rng 8-byte
+ * aligned; outputs must not overlap inputs.  Checked in this order before any GPU work: NULL q / k / v / out / stats (bwd: also dout /
+ * dq / dk / dv) -> TF_MSDA_ERR_NULL_POINTER; with rng a p outside (0, 1), dimensions, alignment -> TF_MSDA_ERR_BAD_DIMS.
+ */
+int tf_mha_core_train_f32(const float *q, const float *k, const float *v, float *out, const unsigned char *key_mask, float *stats,
+                          const int64_t *rng, float p, int N, int Lq, int Lk, int H, int D, int ldq, int ldk, int ldv, int ldo,
+                          float scale, void *stream);
+int tf_mha_core_bwd_f32(const float *dout, const float *q, const float *k, const float *v, const float *out, const float *stats,
+                        const unsigned char *key_mask, const int64_t *rng, float p, float *dq, float *dk, float *dv, int N, int Lq,
+                        int Lk, int H, int D, int lddo, int ldq, int ldk, int ldv, int ldo, int lddq, int lddk, int lddv, float scale,
+                        void *stream);
+
+/*
  * Greedy non-maximum suppression on HOST boxes (all pointers host; synchronous): torchvision.ops.nms semantics, which the
  * reference's tracker calls twice per frame (tracker.py:399,495).  boxes [n, 4] xyxy, scores [n]; boxes are visited in
  * stable descending-score order; keep [n] receives the indices of the kept boxes in that order, *n_keep their number.

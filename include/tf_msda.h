@@ -46,7 +46,7 @@
 extern "C" {
 #endif
 
-#define TF_MSDA_ABI_VERSION 11
+#define TF_MSDA_ABI_VERSION 12
 #define TF_MSDA_MAX_LEVELS 16
 
 typedef enum tf_msda_status {

@@ -93,10 +93,12 @@ EXPORTED_SYMBOLS = (
     "tf_groupnorm_levels_workspace_doubles",
     "tf_groupnorm_levels_nhwc_f32",
     "tf_mha_core_f32",
+    "tf_mha_core_train_f32",
+    "tf_mha_core_bwd_f32",
     "tf_nms_host_f32",
 )
 
-ABI_VERSION = 11   # 11: tf_groupnorm_levels_nhwc_f32 / _workspace_doubles, tf_conv_packed_partials_f32 (10: tf_dropout_keep_u8 / _inplace, tf_add_dropout_layernorm_train / _bwd, tf_relu_dropout_bwd (9: tf_mask_loss_workspace_bytes / _fwd / _bwd (8: tf_set_criterion_fwd / _bwd, tf_match_cost; 7:tf_add_layernorm_train / _bwd; 6: tf_msda_fused_prologue / _backward_epilogue; 5: tf_linear_grad_stats / wgrad / dgrad; 4: tf_msda_backward_det_* and TF_MSDA_ERR_WORKSPACE; 3: the split-product entry points take w_lo / w_scale / terms)
+ABI_VERSION = 12   # 12: tf_mha_core_train_f32 / _bwd_f32 (11: tf_groupnorm_levels_nhwc_f32 / _workspace_doubles, tf_conv_packed_partials_f32 (10: tf_dropout_keep_u8 / _inplace, tf_add_dropout_layernorm_train / _bwd, tf_relu_dropout_bwd (9: tf_mask_loss_workspace_bytes / _fwd / _bwd (8: tf_set_criterion_fwd / _bwd, tf_match_cost; 7:tf_add_layernorm_train / _bwd; 6: tf_msda_fused_prologue / _backward_epilogue; 5: tf_linear_grad_stats / wgrad / dgrad; 4: tf_msda_backward_det_* and TF_MSDA_ERR_WORKSPACE; 3: the split-product entry points take w_lo / w_scale / terms)
 
 _lib = None
 
@@ -282,6 +284,10 @@ def lib():
     L.tf_groupnorm_levels_nhwc_f32.argtypes = [ctypes.POINTER(GnLevel), ci, ci, ci, ci, ctypes.c_float, vp, i64, vp, vp]
     L.tf_mha_core_f32.restype = ci
     L.tf_mha_core_f32.argtypes = [vp, vp, vp, vp, vp] + [ci] * 9 + [ctypes.c_float, vp]
+    L.tf_mha_core_train_f32.restype = ci
+    L.tf_mha_core_train_f32.argtypes = [vp] * 7 + [ctypes.c_float] + [ci] * 9 + [ctypes.c_float, vp]
+    L.tf_mha_core_bwd_f32.restype = ci
+    L.tf_mha_core_bwd_f32.argtypes = [vp] * 8 + [ctypes.c_float] + [vp] * 3 + [ci] * 13 + [ctypes.c_float, vp]
     if L.tf_msda_abi_version() != ABI_VERSION:
         raise RuntimeError("libtf_msda.so ABI version %d != expected %d (rebuild)" %
                            (L.tf_msda_abi_version(), ABI_VERSION))

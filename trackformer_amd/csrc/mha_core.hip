@@ -18,6 +18,8 @@
 // 8 x 32 where the vector kernel above takes 23.1 (27.4 against 64.8 at 800 x 800 x 8 x 36; profiles/r05_mha_matrix_cores.txt).
 // tf_msda_set_option("mha_mfma", 0 / 2) / TF_MHA_MFMA select the vector kernel / the matrix-core kernel with K and V staged in
 // LDS (what key counts above 1024 use).
+// Training (opt-in, fused.set_attention_training): tf_mha_core_train_f32 is mha_mfma_stream_kernel<D, NB, true>, the backward lives in
+// mha_bwd.h (included at the end of this file).
 #include <hip/hip_runtime.h>
 
 #include <float.h>
@@ -25,6 +27,7 @@
 
 #include <stdint.h>
 
+#include "dropout_rng.h"
 #include "host_dispatch.h"
 #include "msda_common.h"
 #include "tf_fused.h"
@@ -336,11 +339,14 @@ mha_mfma_kernel(const float *__restrict__ q, const float *__restrict__ k, const 
 //     key read its 128-byte row of the head in one piece.  (Head dimension 36: the four channels behind 32 are a third tile
 //     with a quarter of its columns in use.)
 // NB = batches of PF tiles per wave whose accumulators stay live: Lk <= 16 * 4 * PF * NB (1: 512 keys at D <= 36, 2: 1024).
-template <int D, int NB>
+// TRAIN (tf_mha_core_train_f32, csrc/mha_bwd.h): the same kernel also saves the rows' softmax statistics and, with rng != NULL, drops
+// weights where they are read for P V -- a lane's four weights there are four consecutive keys of one row: one Philox group.  Every
+// addition is behind `if constexpr (TRAIN)`; the inference instantiation ignores its four trailing arguments.
+template <int D, int NB, bool TRAIN = false>
 __global__ void __launch_bounds__(THREADS)
 mha_mfma_stream_kernel(const float *__restrict__ q, const float *__restrict__ k, const float *__restrict__ v, float *__restrict__ out,
                        const unsigned char *__restrict__ key_mask, int Lq, int Lk, int ldq, int ldk, int ldv, int ldo, float scale,
-                       int lk_pad)
+                       int lk_pad, float *__restrict__ stats, const long long *__restrict__ rng, unsigned drop_T, float drop_scale)
 {
     constexpr int D4 = D / 4, G16 = D / 16, TAIL = (D % 16) / 4, VW = G16, XT = TAIL > 0 ? 1 : 0;
     constexpr int PF = D <= 36 ? 8 : 4, NW = THREADS / 64;
@@ -468,6 +474,14 @@ mha_mfma_stream_kernel(const float *__restrict__ q, const float *__restrict__ k,
     }
     __syncthreads();
     // ---- phase 3: out = P V
+    tfd::Stream drop_st = {0u, 0u, 0u, 0u};
+    unsigned long long drop_row = 0;   // first Philox group of this lane's query row m16
+    if constexpr (TRAIN) {
+        if (rng != nullptr) {
+            drop_st = tfd::load_stream(rng);
+            drop_row = (((unsigned long long)n * gridDim.y + h) * Lq + min(q0 + m16, Lq - 1)) * (unsigned long long)((Lk + 3) >> 2);
+        }
+    }
     f32x4m_t o[VW + XT];
 #pragma unroll
     for (int c = 0; c < VW + XT; ++c) o[c] = f32x4m_t{0.f, 0.f, 0.f, 0.f};
@@ -479,7 +493,16 @@ mha_mfma_stream_kernel(const float *__restrict__ q, const float *__restrict__ k,
         for (int i = 0; i < PF; ++i) {
             const int g = g0 + NW * i;
             if (g < ntiles) {   // wave-uniform
-                const f32x4m_t pa = *reinterpret_cast<const f32x4m_t *>(s_s + (size_t)m16 * lk_pad + 16 * g + 4 * kq);
+                f32x4m_t pa = *reinterpret_cast<const f32x4m_t *>(s_s + (size_t)m16 * lk_pad + 16 * g + 4 * kq);
+                if constexpr (TRAIN) {
+                    if (rng != nullptr) {   // keys 16 g + 4 kq .. + 3 of row m16: group 4 g + kq of the padded row (THE MASK CONTRACT)
+                        const unsigned bits = tfd::keep_bits(drop_st, drop_row + (unsigned long long)(4 * g + kq), drop_T);
+                        pa.x = (bits & 1u) ? pa.x * drop_scale : 0.f;
+                        pa.y = (bits & 2u) ? pa.y * drop_scale : 0.f;
+                        pa.z = (bits & 4u) ? pa.z * drop_scale : 0.f;
+                        pa.w = (bits & 8u) ? pa.w * drop_scale : 0.f;
+                    }
+                }
 #pragma unroll
                 for (int c = 0; c < VW; ++c) {
                     o[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(pa.x, vb.main[i][0][c], o[c], 0, 0, 0);
@@ -519,6 +542,16 @@ mha_mfma_stream_kernel(const float *__restrict__ q, const float *__restrict__ k,
                 total += s_wsum[w * TQ + qi];
             }
             *reinterpret_cast<f32x4m_t *>(out + ((size_t)n * Lq + q0 + qi) * ldo + h * D + c4 * 4) = r * (total > 0.f ? 1.f / total : 0.f);
+            if constexpr (TRAIN) {
+                if (c4 == 0) {   // (row maximum in units of log2, 0 for a row without keys; reciprocal row sum, 0 for such a row)
+                    float m = s_wmax[qi];
+#pragma unroll
+                    for (int w = 1; w < NW; ++w) m = fmaxf(m, s_wmax[w * TQ + qi]);
+                    float *st = stats + 2 * ((((size_t)n * gridDim.y + h) * Lq) + q0 + qi);
+                    st[0] = m == -INFINITY ? 0.f : m;
+                    st[1] = total > 0.f ? 1.f / total : 0.f;
+                }
+            }
         }
     }
 }
@@ -556,8 +589,13 @@ extern "C" int tf_mha_core_f32(const float *q, const float *k, const float *v, f
             }
             if (lds > 64 * 1024 && !tfm::raise_dynamic_lds_limit(fns)) return TF_MSDA_ERR_LAUNCH;
             const dim3 grids((unsigned)((Lq + TQ - 1) / TQ), (unsigned)H, (unsigned)N);
+            float *no_stats = nullptr;
+            const long long *no_rng = nullptr;
+            unsigned no_T = 0u;
+            float no_scale = 0.f;
             void *args[] = {(void *)&q, (void *)&k, (void *)&v, (void *)&out, (void *)&key_mask, (void *)&Lq, (void *)&Lk, (void *)&ldq,
-                            (void *)&ldk, (void *)&ldv, (void *)&ldo, (void *)&scale, (void *)&lkp};
+                            (void *)&ldk, (void *)&ldv, (void *)&ldo, (void *)&scale, (void *)&lkp, (void *)&no_stats, (void *)&no_rng,
+                            (void *)&no_T, (void *)&no_scale};
             return hipLaunchKernel(fns, grids, dim3(THREADS), args, lds, static_cast<hipStream_t>(stream)) == hipSuccess
                        ? TF_MSDA_OK : TF_MSDA_ERR_LAUNCH;
         }
@@ -615,3 +653,5 @@ extern "C" int tf_mha_core_f32(const float *q, const float *k, const float *v, f
     return hipLaunchKernel(fn, grid, dim3(THREADS), argv, lds, static_cast<hipStream_t>(stream)) == hipSuccess
                ? TF_MSDA_OK : TF_MSDA_ERR_LAUNCH;
 }
+
+#include "mha_bwd.h"

@@ -529,6 +529,32 @@ class DeformableTransformerDecoderLayer(nn.Module):
         o = F.scaled_dot_product_attention(q, k, v.transpose(1, 2), attn_mask=mask)
         return mha.out_proj(o.transpose(1, 2).reshape(n, lq, E)), False
 
+    def self_attention_training(self, tgt, query_pos, key_mask):
+        """The self-attention site of the training-graph branch: nn.MultiheadAttention(q = k = tgt + query_pos, v = tgt) on batch-first
+        tensors.  With fused.set_attention_training(True) and tensors the gate takes (fused.attention_train_site): one linear for the
+        shared q | k projection, one for v -- row blocks of in_proj_weight as views, so autograd adds their gradients into
+        in_proj_weight.grad --, the attention core with its own backward (fused.mha_core_train) and the out-projection, without a
+        transpose.  Otherwise the module call, as ever."""
+        mha = self.self_attn
+        route = fused.attention_train_site(mha, tgt, key_mask)
+        x = self.with_pos_embed(tgt, query_pos)
+        if route is None:
+            return mha(x.transpose(0, 1), x.transpose(0, 1), tgt.transpose(0, 1), key_padding_mask=key_mask)[0].transpose(0, 1)
+        kind, p, rng = route
+        if kind == "reference":
+            return fused.attention_reference(x, tgt, mha, key_mask, p, rng)
+        E = mha.embed_dim
+        w, b = mha.in_proj_weight, mha.in_proj_bias
+
+        def project(inp, rows):
+            y = fused.linear_train(inp, w[rows], b[rows]) if fused.train_route(inp) else None
+            return F.linear(inp, w[rows], b[rows]) if y is None else y
+
+        qk = project(x, slice(0, 2 * E))
+        v = project(tgt, slice(2 * E, 3 * E))
+        o = fused.mha_core_train(qk, v, mha.num_heads, key_mask, p, rng)
+        return fused.module_linear(mha.out_proj, o, False)
+
     def forward(self, tgt, query_pos, reference_points, src, src_spatial_shapes,
                 src_padding_mask=None, query_attn_mask=None, filler_key_mask=None, src_value=None):
         """filler_key_mask [N, Lq] (True = ignore as a KEY of the self-attention only): marks filler track queries
@@ -545,9 +571,7 @@ class DeformableTransformerDecoderLayer(nn.Module):
                                                               residual_norm=(tgt, self.norm2))
         else:
             normed = False
-            q = k = self.with_pos_embed(tgt, query_pos)
-            tgt2 = self.self_attn(q.transpose(0, 1), k.transpose(0, 1), tgt.transpose(0, 1),
-                                  key_padding_mask=key_mask)[0].transpose(0, 1)
+            tgt2 = self.self_attention_training(tgt, query_pos, key_mask)
         tgt = tgt2 if normed else fused.residual_norm(tgt, tgt2, self.norm2, _inference(self), dropout=self.dropout2)
         # deformable cross attention into the encoder memory
         inf = _inference(self)

@@ -2104,6 +2104,167 @@ def dropout_ffn_hidden(x, linear_module, relu, dropout):
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
+# TRAINING THROUGH THE DECODER SELF-ATTENTION (opt-in; include/tf_fused.h: TRAINING THROUGH THE ATTENTION CORE; csrc/mha_bwd.h).  With
+# gradients enabled the decoder layer's query self-attention is nn.MultiheadAttention's chain: an in-projection, three transposes,
+# baddbmm, a masked softmax, an ATen dropout that writes a dropped [N H, L, L] copy and a byte mask, bmm, the head-averaged weights
+# nobody reads, the out-projection -- and the reverse of all of it.  set_attention_training(True) / TF_ATTENTION_TRAIN=1 routes the site
+# (DeformableTransformerDecoderLayer.self_attention_training) through two projections (linear_train where train_route() holds),
+# mha_core_train below and the out-projection, batch-first, without a transpose: the forward is the deployed attention core plus the
+# rows' softmax statistics, the backward ONE launch that rebuilds the weights -- nothing of size L x L is stored, no atomics, bit-identical
+# from call to call.  Dropout on the weights follows THE MASK CONTRACT of the header: decided by the counter-based generator, recomputed
+# in the backward.  A site whose nn.MultiheadAttention drops (dropout > 0, training mode) needs set_dropout_training() as well: True --
+# the kernels decide the mask from dropout_rng(); "reference" -- the same draw, the mask of tf_dropout_keep_u8 over the padded rows and
+# torch ops in any floating dtype (the oracle of the layer test); False -- today's line.  NOT covered: plain DETR's transformer.py, the
+# track-attention layers, head dimensions other than 32 and 36, more than 1024 queries, float (additive) masks, host tensors, a forward
+# without gradients.  OFF by default: whether it is faster inside a training step is a measurement (tools/bench_attention_train.py,
+# profiles/attention_train_bench.json), not a promise.
+_attention_train = None    # None: follow TF_ATTENTION_TRAIN (unset: off)
+_attention_train_counts = {"own": 0, "own_dropout": 0, "reference": 0, "torch": 0}
+_ATTENTION_TRAIN_HEAD_DIMS = (32, 36)
+_ATTENTION_TRAIN_MAX_L = 1024
+
+
+def attention_training_enabled():
+    if _attention_train is not None:
+        return _attention_train
+    return os.environ.get("TF_ATTENTION_TRAIN", "0") not in ("", "0")
+
+
+def set_attention_training(flag):
+    """Switch the training path of the decoder's query self-attention on or off (process-wide; None: follow TF_ATTENTION_TRAIN again);
+    returns the previous setting."""
+    global _attention_train
+    prev = attention_training_enabled()
+    _attention_train = None if flag is None else bool(flag)
+    return _switched(prev, attention_training_enabled())
+
+
+def attention_train_counts(reset=False):
+    """With the switch on: how many self-attention sites with gradients ran the library's own kernels without dropout ("own") or with the
+    mask decided inside them ("own_dropout"), the torch-op reference mode ("reference"), or today's nn.MultiheadAttention call ("torch")."""
+    return _read_counts(_attention_train_counts, reset)
+
+
+def _attention_mask_ok(key_padding_mask, x):
+    """None, or a bool / uint8 [N, L] mask on x's device (a float mask is ADDITIVE for nn.MultiheadAttention: not taken)."""
+    return key_padding_mask is None or (key_padding_mask.dtype in (torch.bool, torch.uint8) and key_padding_mask.device == x.device
+                                        and key_padding_mask.shape == x.shape[:2])
+
+
+def attention_train_applies(mha, x, key_padding_mask=None):
+    """The gate of the own route for nn.MultiheadAttention `mha` on the batch-first x [N, L, E]: gradients enabled, fp32 device tensors,
+    the packed in-projection, head dimension 32 or 36, 1 <= L <= 1024, mask None or bool / uint8 [N, L]."""
+    if not (torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.numel() > 0):
+        return False
+    w, b = mha.in_proj_weight, mha.in_proj_bias
+    E, H = mha.embed_dim, mha.num_heads
+    if w is None or b is None or mha.bias_k is not None or mha.add_zero_attn or x.shape[-1] != E or E % H:
+        return False
+    if not (_param_ok(w, x) and _param_ok(b, x) and w.shape == (3 * E, E)):
+        return False
+    return (E // H in _ATTENTION_TRAIN_HEAD_DIMS and x.shape[1] <= _ATTENTION_TRAIN_MAX_L and x.shape[0] <= 65535
+            and _attention_mask_ok(key_padding_mask, x))
+
+
+def attention_train_site(mha, x, key_padding_mask=None):
+    """How one self-attention site of a training-graph forward runs, counted: None -- today's nn.MultiheadAttention call (uncounted with
+    the switch off, "torch" with it on) --, ("own", 0.0, None), ("own_dropout", p, rng) or ("reference", p, rng).  rng is drawn HERE,
+    once per site that drops, in both modes: the own route and the reference mode see the same masks under one seed.  A forward without
+    gradients (the tracking model's previous-frame pass) keeps today's call, uncounted, as at the other training sites."""
+    if not attention_training_enabled() or not torch.is_grad_enabled():
+        return None
+    drops = mha.training and mha.dropout > 0.0
+    mode = dropout_training_enabled() if drops else True
+    route = None
+    if mode == "reference":
+        w = mha.in_proj_weight
+        if (torch.is_grad_enabled() and x.is_cuda and x.is_floating_point() and x.dim() == 3 and x.numel() > 0 and w is not None
+                and mha.in_proj_bias is not None and w.dtype == x.dtype and mha.bias_k is None and not mha.add_zero_attn
+                and mha.dropout < 1.0 and _attention_mask_ok(key_padding_mask, x)):
+            route = ("reference", float(mha.dropout), dropout_rng(x.device))
+    elif mode and (not drops or mha.dropout < 1.0) and attention_train_applies(mha, x, key_padding_mask):
+        route = ("own_dropout", float(mha.dropout), dropout_rng(x.device)) if drops else ("own", 0.0, None)
+    _attention_train_counts[route[0] if route else "torch"] += 1
+    return route
+
+
+class _MhaCoreTrain(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, qk, v, num_heads, mask, p, rng):
+        n, length, e2 = qk.shape
+        e = e2 // 2
+        d = e // num_heads
+        with torch.cuda.device(qk.device):
+            out = torch.empty((n, length, e), dtype=torch.float32, device=qk.device)
+            stats = torch.empty((n, num_heads, length, 2), dtype=torch.float32, device=qk.device)
+            q_ptr = qk.data_ptr()
+            rc = _cabi.lib().tf_mha_core_train_f32(q_ptr, q_ptr + e * 4, v.data_ptr(), out.data_ptr(), _ptr(mask), stats.data_ptr(), _ptr(rng),
+                                                   float(p), n, length, length, num_heads, d, e2, e2, e, e, float(d) ** -0.5,
+                                                   _stream(qk.device))
+        _cabi.check(rc, "tf_mha_core_train_f32")
+        ctx.num_heads, ctx.p = num_heads, float(p)
+        ctx.save_for_backward(qk, v, out, stats, mask, rng)   # the operands, the output and two floats per row: nothing of size L x L
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        qk, v, out, stats, mask, rng = ctx.saved_tensors
+        n, length, e2 = qk.shape
+        e = e2 // 2
+        d = e // ctx.num_heads
+        dout = _aligned(dout)
+        with torch.cuda.device(qk.device):
+            dqk, dv = torch.empty_like(qk), torch.empty_like(v)   # dq | dk: the halves of the shared projection's gradient, no cat
+            q_ptr, g_ptr = qk.data_ptr(), dqk.data_ptr()
+            rc = _cabi.lib().tf_mha_core_bwd_f32(dout.data_ptr(), q_ptr, q_ptr + e * 4, v.data_ptr(), out.data_ptr(), stats.data_ptr(),
+                                                 _ptr(mask), _ptr(rng), ctx.p, g_ptr, g_ptr + e * 4, dv.data_ptr(), n, length, length,
+                                                 ctx.num_heads, d, e, e2, e2, e, e, e2, e2, e, float(d) ** -0.5, _stream(qk.device))
+        _cabi.check(rc, "tf_mha_core_bwd_f32")
+        return dqk, dv, None, None, None, None
+
+
+def mha_core_train(qk, v, num_heads, key_padding_mask=None, p=0.0, rng=None):
+    """dropout_p(softmax(q k^T / sqrt(d))) v with the library's own backward (include/tf_fused.h: tf_mha_core_train_f32 /
+    tf_mha_core_bwd_f32).  qk [N, L, 2E]: the shared q | k projection, v [N, L, E], fp32, contiguous, on the device; head dimension 32 or
+    36, L <= 1024; key_padding_mask [N, L] bool / uint8 (True = ignore) or None; rng: the int64[2] (seed, offset) tensor of
+    dropout_rng(), or None for no dropout (p is not read then).  Saves qk, v, out, the rows' statistics, the uint8 mask and rng; its
+    backward returns (dqk, dv).  Anything the kernels do not take is an error (attention_train_applies is the gate)."""
+    if not (qk.is_cuda and qk.dtype == torch.float32 and v.dtype == torch.float32 and v.device == qk.device and qk.dim() == 3
+            and v.dim() == 3):
+        raise ValueError("mha_core_train: fp32 device tensors [N, L, 2E] and [N, L, E] expected")
+    qk, v = _aligned(qk), _aligned(v)
+    n, length, e2 = qk.shape
+    if e2 % 2 or v.shape != (n, length, e2 // 2) or (e2 // 2) % num_heads:
+        raise ValueError("mha_core_train: shapes %s / %s with %d heads" % (tuple(qk.shape), tuple(v.shape), num_heads))
+    mask = None
+    if key_padding_mask is not None:
+        if not _attention_mask_ok(key_padding_mask, qk):
+            raise ValueError("mha_core_train: key_padding_mask must be bool / uint8 [N, L] on the device")
+        mask = key_padding_mask.to(torch.uint8).contiguous()
+    return _MhaCoreTrain.apply(qk, v, num_heads, mask, p, rng)
+
+
+def attention_reference(x, value_in, mha, key_padding_mask, p, rng):
+    """The "reference" mode of the site: out_proj(dropout(softmax(q k^T / sqrt(d))) v) in torch ops, batch-first, any floating dtype, with
+    the mask of tf_dropout_keep_u8 over the padded weight tensor [N, H, L, 4 ceil(L / 4)] (THE MASK CONTRACT)."""
+    E, H = mha.embed_dim, mha.num_heads
+    n, length, _ = x.shape
+    d = E // H
+    w, b = mha.in_proj_weight, mha.in_proj_bias
+    qk = F.linear(x, w[:2 * E], b[:2 * E]).view(n, length, 2, H, d)
+    v = F.linear(value_in, w[2 * E:], b[2 * E:]).view(n, length, H, d)
+    s = (qk[:, :, 0].permute(0, 2, 1, 3) @ qk[:, :, 1].permute(0, 2, 3, 1)) * (float(d) ** -0.5)
+    if key_padding_mask is not None:
+        s = s.masked_fill(key_padding_mask.to(torch.bool)[:, None, None, :], float("-inf"))
+    lk4 = 4 * ((length + 3) // 4)
+    keep = dropout_keep(rng, p, n * H * length * lk4).view(n, H, length, lk4)[..., :length]
+    weights = torch.softmax(s, -1) * (keep.to(x.dtype) * dropout_scale(p))
+    o = (weights @ v.permute(0, 2, 1, 3)).permute(0, 2, 1, 3).reshape(n, length, E)
+    return mha.out_proj(o)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
 # THE TRAINING PATH OF THE BACKBONE'S CONVOLUTIONS (opt-in; include/tf_fused.h: THE BACKWARD OF A 3 x 3 CONVOLUTION; csrc/conv_bwd.h).
 # The switch lives with its caller (backbone.set_split_conv_training / TF_SPLIT_CONV_TRAIN=1: the trainable bottlenecks' conv + FrozenBN
 # pairs); conv_train below is the operator.  3 x 3, padding 1, stride 1 or 2: the forward is conv3x3() (bit-identical to the inference
