@@ -1311,7 +1311,10 @@ NU_FWD = [
     ("rowgather_f32", "msda_fwd_rowgather<f32>", {}, dict(N=2, M=3, D=5, Lq=21, P=3, shapes=[(7, 3), (1, 1), (2, 9)])),
     ("buf", "msda_fwd_f32_buf<plain>", {}, dict(N=1, M=4, D=64, Lq=30, P=4, shapes=[(12, 10), (6, 5)])),
     ("direct", "msda_fwd_f32_direct<plain>", {}, dict(N=1, M=8, D=32, Lq=40, P=4, shapes=EPYR)),
-    ("direct9", "msda_fwd_f32_direct9<plain>", {}, dict(N=1, M=8, D=36, Lq=30, P=4, shapes=EPYR * 2)),
+    ("direct_l3", "msda_fwd_f32_direct<plain>", {}, dict(N=1, M=8, D=32, Lq=37, P=4, shapes=EPYR[:3])),   # odd L: half a level pair
+    ("direct_l1", "msda_fwd_f32_direct<plain>", {}, dict(N=1, M=8, D=32, Lq=33, P=4, shapes=EPYR[:1])),
+    ("direct9", "msda_fwd_f32_direct9<plain>", {}, dict(N=1, M=8, D=36, Lq=30, P=4, shapes=EPYR * 2)),   # 30 queries: 28 + 2
+    ("direct9_l3", "msda_fwd_f32_direct9<plain>", {}, dict(N=1, M=8, D=36, Lq=9, P=4, shapes=EPYR[:3])),
     ("quad", "msda_fwd_f32_quad<plain>", {"tiled": 1, "pquad": 0}, dict(N=1, M=8, D=32, Lq=S_EPYR, P=4, shapes=EPYR, encoder=True)),
     ("pquad", "msda_fwd_f32_pquad<plain>", {"pquad_v2": 0}, dict(N=1, M=8, D=32, Lq=S_EPYR, P=4, shapes=EPYR, encoder=True)),
     ("pquad_d36", "msda_fwd_f32_pquad<plain,D=36>", {}, dict(N=1, M=8, D=36, Lq=S_EPYR, P=4, shapes=EPYR, encoder=True)),
@@ -1327,7 +1330,9 @@ NU_BWD = [
 NU_FUSED = [
     ("buf", "msda_fwd_f32_buf<fused>", {}, dict(N=1, M=4, D=16, Lq=30, P=2, shapes=EPYR, ref_dim=4)),
     ("direct", "msda_fwd_f32_direct<fused>", {}, dict(N=1, M=8, D=32, Lq=40, P=4, shapes=EPYR, ref_dim=2)),
+    ("direct_l3", "msda_fwd_f32_direct<fused>", {}, dict(N=1, M=8, D=32, Lq=37, P=4, shapes=EPYR[:3], ref_dim=4)),
     ("direct9", "msda_fwd_f32_direct9<fused>", {}, dict(N=1, M=8, D=36, Lq=30, P=4, shapes=EPYR * 2, ref_dim=4)),
+    ("direct9_l3", "msda_fwd_f32_direct9<fused>", {}, dict(N=1, M=8, D=36, Lq=9, P=4, shapes=EPYR[:3], ref_dim=2)),
     ("pquad2", "msda_fwd_f32_pquad2<fused,4w,2p>", {}, dict(N=1, M=8, D=32, Lq=S_EPYR, P=4, shapes=EPYR, encoder=True)),
 ]
 

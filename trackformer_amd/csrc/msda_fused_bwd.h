@@ -13,7 +13,8 @@
 // written exactly once by a plain vector store; every sum runs in index order (the head's L P samples for the softmax and its
 // gradient, (m, p) for grad_ref), so the results are a function of the tensor contents and the dimensions alone.  `rows` only
 // decides which workgroup computes a row, not how.
-// The epilogue recomputes each sample's location (fused_location: the prologue's own arithmetic) for the range test only.
+// The epilogue recomputes each sample's location (fused_location, msda_point.h: the prologue's own arithmetic) for the range
+// test only.
 #ifndef TF_MSDA_FUSED_BWD_H_
 #define TF_MSDA_FUSED_BWD_H_
 
@@ -33,21 +34,6 @@ struct FusedBwdArgs {
 struct FusedLevels {
     float hw[2 * TF_MSDA_MAX_LEVELS];
 };
-
-// The sampling location of one sample: the module's formulas, operation by operation (both kernels: bit-identical results).
-__device__ __forceinline__ float2 fused_location(const float *rp, int ref_dim, float2 off, float h, float w, float inv_p)
-{
-#pragma clang fp contract(off)
-    float2 xy;
-    if (ref_dim == 2) {
-        xy.x = rp[0] + off.x / h;                       // x over H_l, as written
-        xy.y = rp[1] + off.y / w;
-    } else {
-        xy.x = rp[0] + off.x * inv_p * rp[2] * 0.5f;
-        xy.y = rp[1] + off.y * inv_p * rp[3] * 0.5f;
-    }
-    return xy;
-}
 
 __global__ void __launch_bounds__(kThreads)
 msda_fused_prologue_kernel(const FusedBwdArgs fa, const FusedLevels lv, float *__restrict__ loc, float *__restrict__ attn)
@@ -118,13 +104,12 @@ msda_fused_bwd_epilogue_kernel(const FusedBwdArgs fa, const FusedLevels lv, cons
         const long long row = row0 + r;
         // A sample out of range takes no part in the forward: its gradients are zero, whatever the operator backward left there (its
         // kernels form grad_out times zeroed corners: 0, but NaN under a NaN in grad_out).  The test is the operator kernels' own
-        // (make_tap: one fma per coordinate) on the prologue's own location, so for finite gradients nothing changes.
+        // (pixel_point: one fma per coordinate) on the prologue's own location, so for finite gradients nothing changes.
         const float hl = lv.hw[2 * l], wl = lv.hw[2 * l + 1];
         const float *rp = fa.ref + (row * fa.L + l) * fa.ref_dim;
         const float2 off = *reinterpret_cast<const float2 *>(fa.qproj + row * fa.ld + fa.off_col + 2 * j);
         const float2 xy = fused_location(rp, fa.ref_dim, off, hl, wl, inv_p);
-        const float xr = __builtin_fmaf(xy.x, wl, -0.5f), yr = __builtin_fmaf(xy.y, hl, -0.5f);
-        const bool in = (yr > -1.f) && (xr > -1.f) && (yr < hl) && (xr < wl);
+        const bool in = pixel_point(xy.x, xy.y, wl, hl, true).in;
         const float a = attn[row0 * MLP + i], g = in ? grad_attn[row0 * MLP + i] : 0.f;
         s_a[i] = a;
         s_g[i] = g;

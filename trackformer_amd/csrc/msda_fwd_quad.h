@@ -202,13 +202,10 @@ msda_fwd_f32_quad(const DirectArgs da, const LevelTable lt, const QuadGeom qg)
                 sa[ps][l] = sa[ps][l] / sum;
                 const int lc = l < L ? l : 0;
                 const float *rp = da.fa.ref + ((size_t)bq * L + lc) * da.fa.ref_dim;
-                if (da.fa.ref_dim == 2) {
-                    sx[ps][l] = rp[0] + sx[ps][l] / (float)Hs[l];   // x / H_l (as the reference writes it)
-                    sy[ps][l] = rp[1] + sy[ps][l] / (float)Ws[l];   // y / W_l
-                } else {
-                    sx[ps][l] = rp[0] + sx[ps][l] / (float)PT * rp[2] * 0.5f;
-                    sy[ps][l] = rp[1] + sy[ps][l] / (float)PT * rp[3] * 0.5f;
-                }
+                const float2 xy = fused_location(rp, da.fa.ref_dim, make_float2(sx[ps][l], sy[ps][l]), (float)Hs[l], (float)Ws[l],
+                                                 1.f / (float)PT);
+                sx[ps][l] = xy.x;
+                sy[ps][l] = xy.y;
             }
         }
     }
@@ -222,10 +219,9 @@ msda_fwd_f32_quad(const DirectArgs da, const LevelTable lt, const QuadGeom qg)
                 const float Wf = (float)Ws[l], Hf = (float)Hs[l];
 #pragma unroll
                 for (int ps = 0; ps < NPASS; ++ps) {
-                    const float xr = __builtin_fmaf(sx[ps][l], Wf, -0.5f);
-                    const float yr = __builtin_fmaf(sy[ps][l], Hf, -0.5f);
-                    const bool in = live[ps] && (yr > -1.f) && (xr > -1.f) && (yr < Hf) && (xr < Wf);
-                    const int x0 = (int)__builtin_floorf(in ? xr : 0.f), y0 = (int)__builtin_floorf(in ? yr : 0.f);
+                    const PixelPoint<float> pt = pixel_point(sx[ps][l], sy[ps][l], Wf, Hf, live[ps]);
+                    const int x0 = pt.x0, y0 = pt.y0;
+                    const bool in = pt.in;
                     mnx = min(mnx, in ? x0 : INT_MAX);
                     mxx = max(mxx, in ? x0 : INT_MIN);
                     mny = min(mny, in ? y0 : INT_MAX);
@@ -371,6 +367,8 @@ msda_fwd_f32_quad(const DirectArgs da, const LevelTable lt, const QuadGeom qg)
         if (ps * PAIRS >= nq) return;                // uniform
         const int H = Hs[l], W = Ws[l];
         const float Wf = (float)W, Hf = (float)H;
+        // pixel_point / point_corners (msda_point.h) written out: through the helpers the fused instantiations spill 12 and 4
+        // bytes more (tests/test_msda_point_single_definition.py lists the site); phase A above calls pixel_point
         const float xr = __builtin_fmaf(sx[ps][l], Wf, -0.5f);   // cuh:227-228, single rounding
         const float yr = __builtin_fmaf(sy[ps][l], Hf, -0.5f);
         const bool in = live[ps] && (yr > -1.f) && (xr > -1.f) && (yr < Hf) && (xr < Wf);

@@ -23,7 +23,7 @@
 //   msda_fwd_f32_direct         fp32, D == 32, P == 4 (every TrackFormer config with hidden 256): no
 //                               staging prologue, tap arithmetic computed once per pair and shared
 //                               inside the wave.  THE DEFAULT for decoder-shaped calls.
-//   msda_fwd_f32_direct9        the same for D == 36 (hidden 288): nine lanes per pair.
+//   msda_fwd_f32_direct9        the same for D == 36 (hidden 288): nine lanes per pair (one body, direct_body, for both).
 //   msda_fwd_f32_pquad          encoder shape (Lq == S): persistent workgroups, data-adaptive LDS windows, 4 lanes per
 //                               pair (msda_pquad.hip).  THE DEFAULT for encoder-shaped calls.
 //   msda_fwd_f32_quad           the one-tile-per-workgroup form of it (msda_fwd_quad.h): taken when pquad declines
@@ -36,6 +36,9 @@
 //                               radix-sorted by destination row and summed in a fixed order (msda_bwd_det.h); bitwise reproducible.
 // Removed in round 4 (superseded, no default route reached them; measurements in DESIGN.md section 4.1):
 // msda_fwd_f32_win (the first LDS-window kernel, 8 lanes per pair) and msda_bwd_f32_sorted (the first sorted backward).
+// The arithmetic of one sampling point (location formula, pixel mapping, in-range rule, corner validity, Tap / make_tap) is
+// defined once, in msda_point.h, for the kernels of this file, msda_fwd_quad.h, msda_pquad.hip, msda_pquad2.h, msda_bwd_det.h
+// and msda_fused_bwd.h.
 // Common rules: level geometry comes from the kernel arguments (host-shape entry points) or from the
 // reference's device-resident int64 tensor (..._dshapes) -- never a host<->device sync; no kernel
 // branches per tap; nothing depends on CUDA-style 32-wide warps.
@@ -54,6 +57,7 @@
 #include "tf_msda.h"
 #include "msda_common.h"
 #include "msda_dispatch.h"
+#include "msda_point.h"
 #include "msda_quad_geom.h"
 
 namespace {
@@ -75,11 +79,6 @@ thread_local const char *g_last_kernel = "";
 // ---------------------------------------------------------------------------------------------
 // device helpers
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ float fma_t(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
-__device__ __forceinline__ double fma_t(double a, double b, double c) { return __builtin_fma(a, b, c); }
-__device__ __forceinline__ float floor_t(float a) { return __builtin_floorf(a); }
-__device__ __forceinline__ double floor_t(double a) { return __builtin_floor(a); }
-
 __device__ __forceinline__ void fill_level_table(int *s_tab, const LevelTable &lt,
                                                  const int64_t *__restrict__ dshapes, int L)
 {
@@ -102,54 +101,6 @@ __device__ __forceinline__ void fill_level_table(int *s_tab, const LevelTable &l
             }
         }
     }
-}
-
-// One sampling point: pixel coordinates, clamped tap offsets (in units of pixels within the level),
-// bilinear fractions and tap validity.  Follows SURVEY.md Appendix A / cuh:227-229, :24-67.
-template <typename T>
-struct Tap {
-    T fx, fy, gx, gy;       // lw, lh, hw, hh of the reference
-    int o1, o2, o3, o4;     // clamped pixel offsets y*W + x of the four taps
-    bool k1, k2, k3, k4;    // tap contributes (sample in range AND corner inside the level)
-};
-
-template <typename T>
-__device__ __forceinline__ Tap<T> make_tap(T lx, T ly, int H, int W)
-{
-    Tap<T> t;
-    // loc*size - 0.5 with a SINGLE rounding (one fma).  The reference's fp32 instantiation rounds twice
-    // (cuh:227-228: `loc * spatial` is a float product, then `- 0.5` in double, narrowed to float), its
-    // pure-PyTorch path (func.py:40-49, grid_sample at 2*loc-1) rounds three times: the three agree to 1 ulp
-    // of the pixel coordinate, i.e. they can differ only for samples within 1 ulp of an integer pixel
-    // boundary, where the bilinear weight of the disputed tap is <= 1 ulp as well (outputs differ by ~1e-7;
-    // the in-range test at exactly -1 / size can flip, a measure-zero set the golden tests exclude).
-    // The oracle (oracle/msda_ref.c) uses the same single rounding; fp64 is exact in all three.
-    const T xr = fma_t(lx, (T)W, (T)-0.5);
-    const T yr = fma_t(ly, (T)H, (T)-0.5);
-    const bool in = (yr > (T)-1) && (xr > (T)-1) && (yr < (T)H) && (xr < (T)W);
-    // Out-of-range samples may carry huge / non-finite coordinates: neutralise them so that every
-    // derived quantity stays finite (their taps are all invalid anyway).
-    const T x = in ? xr : (T)0, y = in ? yr : (T)0;
-    const T xf = floor_t(x), yf = floor_t(y);
-    t.fx = x - xf;
-    t.fy = y - yf;
-    t.gx = (T)1 - t.fx;
-    t.gy = (T)1 - t.fy;
-    const int x0 = (int)xf, y0 = (int)yf;
-    const int x1 = x0 + 1, y1 = y0 + 1;
-    const bool kx0 = in && (x0 >= 0), kx1 = in && (x1 <= W - 1);
-    const bool ky0 = in && (y0 >= 0), ky1 = in && (y1 <= H - 1);
-    const int cx0 = max(x0, 0), cx1 = min(x1, W - 1);
-    const int cy0 = max(y0, 0), cy1 = min(y1, H - 1);
-    t.o1 = cy0 * W + cx0;
-    t.o2 = cy0 * W + cx1;
-    t.o3 = cy1 * W + cx0;
-    t.o4 = cy1 * W + cx1;
-    t.k1 = ky0 && kx0;
-    t.k2 = ky0 && kx1;
-    t.k3 = ky1 && kx0;
-    t.k4 = ky1 && kx1;
-    return t;
 }
 
 // XCD-aware block order.  The dispatcher places workgroup i on XCD i % 8 (observed behaviour, used
@@ -341,16 +292,10 @@ msda_fwd_f32_buf(const float *__restrict__ value, unsigned value_bytes,
             const float *row = fa.qproj + bq * fa.ld;
             const float2 off = *reinterpret_cast<const float2 *>(row + fa.off_col + (mm * LP + lp) * 2);
             const float *rp = fa.ref + (bq * L + l) * fa.ref_dim;
-            float x, y;
-            if (fa.ref_dim == 2) {
-                x = rp[0] + off.x / (float)s_tab[l];                           // x / H_l  (as written)
-                y = rp[1] + off.y / (float)s_tab[TF_MSDA_MAX_LEVELS + l];      // y / W_l
-            } else {
-                x = rp[0] + off.x / (float)PT * rp[2] * 0.5f;
-                y = rp[1] + off.y / (float)PT * rp[3] * 0.5f;
-            }
-            s_loc[2 * sidx] = x;
-            s_loc[2 * sidx + 1] = y;
+            const float2 xy = fused_location(rp, fa.ref_dim, off, (float)s_tab[l], (float)s_tab[TF_MSDA_MAX_LEVELS + l],
+                                             1.f / (float)PT);
+            s_loc[2 * sidx] = xy.x;
+            s_loc[2 * sidx + 1] = xy.y;
             s_attn[sidx] = row[fa.logit_col + mm * LP + lp];
         }
         __syncthreads();
@@ -394,29 +339,20 @@ msda_fwd_f32_buf(const float *__restrict__ value, unsigned value_bytes,
         for (int p = 0; p < PT; ++p) {
             const float2 xy = sl[l * PT + p];
             const float a = sa[l * PT + p];
-            const float xr = __builtin_fmaf(xy.x, Wf, -0.5f);   // cuh:227-228, single rounding
-            const float yr = __builtin_fmaf(xy.y, Hf, -0.5f);
-            const bool in = (yr > -1.f) && (xr > -1.f) && (yr < Hf) && (xr < Wf);  // cuh:229
-            const float x = in ? xr : 0.f, y = in ? yr : 0.f;
-            const float xf = __builtin_floorf(x), yf = __builtin_floorf(y);
-            const float fx = x - xf, fy = y - yf, gx = 1.f - fx, gy = 1.f - fy;
-            const int x0 = (int)xf, y0 = (int)yf;
-            const bool kx0 = in && (x0 >= 0), kx1 = in && (x0 + 1 <= W - 1);
-            const bool ky0 = in && (y0 >= 0), ky1 = in && (y0 + 1 <= H - 1);
-            const int r0 = y0 * W + x0;        // may be "negative": only used when the tap is valid
-            const int r1 = r0 + W;
-            const unsigned o1 = (ky0 && kx0) ? lvl_base + (unsigned)r0 * rowbytes : kOobOffset;
-            const unsigned o2 = (ky0 && kx1) ? lvl_base + (unsigned)(r0 + 1) * rowbytes : kOobOffset;
-            const unsigned o3 = (ky1 && kx0) ? lvl_base + (unsigned)r1 * rowbytes : kOobOffset;
-            const unsigned o4 = (ky1 && kx1) ? lvl_base + (unsigned)(r1 + 1) * rowbytes : kOobOffset;
+            const PixelPoint<float> pt = pixel_point(xy.x, xy.y, Wf, Hf, true);
+            const PointCorners c = point_corners(pt.x0, pt.y0, W, H, pt.in);
+            const unsigned o1 = (c.ky0 && c.kx0) ? lvl_base + (unsigned)c.r0 * rowbytes : kOobOffset;
+            const unsigned o2 = (c.ky0 && c.kx1) ? lvl_base + (unsigned)(c.r0 + 1) * rowbytes : kOobOffset;
+            const unsigned o3 = (c.ky1 && c.kx0) ? lvl_base + (unsigned)c.r1 * rowbytes : kOobOffset;
+            const unsigned o4 = (c.ky1 && c.kx1) ? lvl_base + (unsigned)(c.r1 + 1) * rowbytes : kOobOffset;
             v[p][0] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, o1, 0, 0);
             v[p][1] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, o2, 0, 0);
             v[p][2] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, o3, 0, 0);
             v[p][3] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, o4, 0, 0);
-            w[p][0] = gy * gx * a;
-            w[p][1] = gy * fx * a;
-            w[p][2] = fy * gx * a;
-            w[p][3] = fy * fx * a;
+            w[p][0] = pt.gy * pt.gx * a;
+            w[p][1] = pt.gy * pt.fx * a;
+            w[p][2] = pt.fy * pt.gx * a;
+            w[p][3] = pt.fy * pt.fx * a;
         }
 #pragma unroll
         for (int p = 0; p < PT; ++p) {
@@ -450,34 +386,113 @@ msda_fwd_f32_buf(const float *__restrict__ value, unsigned value_bytes,
 // launch through the texture-addresser / L1 at <= 64 B/clk/CU (TA_BUSY ~80 % of the kernel's cycles).
 // (struct DirectArgs: msda_common.h)
 
-template <int LPAIRS, bool FUSED>   // LPAIRS = ceil(L / 2)
-__global__ void __launch_bounds__(kThreads, 4)
-msda_fwd_f32_direct(const DirectArgs da, const LevelTable lt, const int64_t *__restrict__ dshapes)
+// Lane geometry of msda_fwd_f32_direct: 8 lanes per pair, 8 pairs per wave (groups aligned to DPP rows), every lane produces.
+struct DirectGeom8 {
+    static constexpr int D = 32, GL = 8, GPW = 8;   // channels per head, lanes per pair, pairs per wave
+    static constexpr bool kAllLanesWork = true;     // every lane belongs to a pair and produces: no test in the kernel
+    int grp, dv;                                    // pair of the wave, lane of the pair
+    __device__ __forceinline__ DirectGeom8()
+    {
+        const int lane = threadIdx.x & 63;
+        grp = lane >> 3;
+        dv = lane & 7;
+    }
+    __device__ __forceinline__ bool exists() const { return true; }
+    __device__ __forceinline__ bool producer() const { return true; }
+    __device__ __forceinline__ int block_pair() const { return threadIdx.x / GL; }   // pair of the workgroup
+    // slot of lane 0 of this group in the wave's exchange buffer: a pad slot after every 8 lanes keeps the 8 groups of a
+    // wave on disjoint banks when they all read slot k
+    __device__ __forceinline__ int xbase() const { return (threadIdx.x >> 6) * 72 + grp * 9; }
+    __device__ __forceinline__ float group_max(float v) const   // xor butterflies over the 8 lanes
+    {
+        v = fmaxf(v, __shfl_xor(v, 1));
+        v = fmaxf(v, __shfl_xor(v, 2));
+        return fmaxf(v, __shfl_xor(v, 4));
+    }
+    __device__ __forceinline__ float group_sum(float v) const
+    {
+        v += __shfl_xor(v, 1);
+        v += __shfl_xor(v, 2);
+        return v + __shfl_xor(v, 4);
+    }
+};
+
+// ---------------------------------------------------------------------------------------------
+// forward, fp32, D == 36 (hidden 288: cfg 4), P == 4, L <= 8: msda_fwd_f32_direct's mapping with 9 lanes per pair
+// ---------------------------------------------------------------------------------------------
+// The decoder calls of the `multi_frame` model (D = 36, L = 8: two frames x 4 levels, 500 + 300 queries) ran
+// msda_fwd_f32_buf: every lane repeats the tap arithmetic (965 vector instructions per wave against 380 in
+// msda_fwd_f32_direct) behind a staging prologue.  This kernel keeps `direct`'s structure -- points fetched straight
+// into registers, the tap arithmetic of a point computed once per pair and published through a per-wave LDS
+// exchange, 16 row gathers in flight per lane -- for 144-byte rows: a (query, head) pair is served by NINE lanes
+// (4 channels each), seven pairs per wave (lane 63 idles), 28 pairs per 256-thread workgroup.  Lanes 0-7 of a group
+// produce (lanes 0-3: the points of level 2i, lanes 4-7: those of level 2i + 1), all nine consume.  The groups are
+// not aligned to DPP rows, so the softmax statistics of the fused entry go through wave shuffles (ds_bpermute).
+// OPT-IN until it has been timed on hardware: tf_msda_set_option("direct9", 1) / TF_MSDA_DIRECT9=1.
+struct DirectGeom9 {
+    static constexpr int D = 36, GL = 9, GPW = 7;
+    static constexpr bool kAllLanesWork = false;    // lane 8 of a group only consumes, lane 63 idles
+    int grp, dv;                                    // lane 63: grp 7, dv 0 (idle)
+    __device__ __forceinline__ DirectGeom9()
+    {
+        const int lane = threadIdx.x & 63;
+        grp = lane / GL;
+        dv = lane - grp * GL;
+    }
+    __device__ __forceinline__ bool exists() const { return grp < GPW; }
+    __device__ __forceinline__ bool producer() const { return dv < 8 && grp < GPW; }
+    __device__ __forceinline__ int block_pair() const { return (threadIdx.x >> 6) * GPW + grp; }   // (lane 63: not live)
+    // per wave: 7 groups x 9 slots (8 used) + padding; lane 63 reads along with group 6 (valid offsets, results never stored)
+    __device__ __forceinline__ int xbase() const { return (threadIdx.x >> 6) * 72 + (grp < GPW ? grp : GPW - 1) * GL; }
+    __device__ __forceinline__ float group_max(float v) const   // the eight producer lanes, in lane order
+    {
+        float mx = -__builtin_inff();
+#pragma unroll
+        for (int k = 0; k < 8; ++k) mx = fmaxf(mx, __shfl(v, grp * GL + k));
+        return mx;
+    }
+    __device__ __forceinline__ float group_sum(float v) const
+    {
+        float sum = 0.f;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) sum += __shfl(v, grp * GL + k);
+        return sum;
+    }
+};
+
+// ---------------------------------------------------------------------------------------------
+// The body of msda_fwd_f32_direct and msda_fwd_f32_direct9.  G is the lane geometry (DirectGeom8 / DirectGeom9); each keeps
+// its own reduction order, so neither kernel's bits depend on the other's.  Lanes 0-7 of a group produce (lanes 0-3: the
+// points of level 2i, lanes 4-7: those of level 2i + 1), all G::GL lanes consume.
+// ---------------------------------------------------------------------------------------------
+template <typename G, int LPAIRS, bool FUSED>   // LPAIRS = ceil(L / 2)
+__device__ __forceinline__ void direct_body(const DirectArgs &da, const LevelTable &lt, const int64_t *__restrict__ dshapes)
 {
-    constexpr int PT = 4, D = 32, DV = 8;
+    constexpr int PT = 4, D = G::D;
     __shared__ int s_tab[3 * TF_MSDA_MAX_LEVELS];
-    // per-wave exchange buffers, one 16-byte slot of offsets and one of weights per lane; a pad slot
-    // after every 8 lanes keeps the 8 groups of a wave on disjoint banks when they all read slot k
+    // per-wave exchange buffers, one 16-byte slot of offsets and one of weights per producer lane (G::xbase)
     __shared__ u32x4_t s_xo[(kThreads / 64) * 72];
     __shared__ f32x4_t s_xw[(kThreads / 64) * 72];
     const int L = da.L, M = da.M, LP = L * PT;
     fill_level_table(s_tab, lt, dshapes, L);
 
+    const G g;
     const int head = blockIdx.x % M;                                   // one head per XCD when M == 8
-    const long long bq = (long long)(blockIdx.x / M) * (kThreads / DV) + threadIdx.x / DV;
-    const int dv = threadIdx.x & 7, sub = dv & 3, which = dv >> 2;
-    const bool live = bq < da.nlq;
+    const int dv = g.dv, sub = dv & 3, which = (dv >> 2) & 1;
+    const long long bq = (long long)(blockIdx.x / M) * ((kThreads / 64) * G::GPW) + g.block_pair();
+    const bool live = (G::kAllLanesWork || g.exists()) && bq < da.nlq;
+    const bool producer = G::kAllLanesWork || g.producer();   // a constant for DirectGeom8
     const long long bqc = live ? bq : 0;
     const long long pair = bqc * M + head;
     const int b = (int)(bqc / da.Lq);
 
-    // ---- this lane's sampling points: (level 2i + which, point sub) for i < LPAIRS -------------
+    // ---- this lane's sampling points: (level 2i + which, point sub) for i < LPAIRS (the producer lanes) -------------
     float sx[LPAIRS], sy[LPAIRS], sa[LPAIRS];
     bool have[LPAIRS];
 #pragma unroll
     for (int i = 0; i < LPAIRS; ++i) {
         const int ml = 2 * i + which;
-        have[i] = ml < L;
+        have[i] = producer && ml < L;
         const int s = (have[i] ? ml : 0) * PT + sub;
         if constexpr (!FUSED) {
             const float2 xy = *reinterpret_cast<const float2 *>(da.loc + (pair * LP + s) * 2);
@@ -496,42 +511,36 @@ msda_fwd_f32_direct(const DirectArgs da, const LevelTable lt, const int64_t *__r
 
     if constexpr (FUSED) {
 #pragma clang fp contract(off)   // keep the reference's operation order (no fused multiply-add)
-        // softmax over the pair's L*P logits: this lane holds LPAIRS of them, the group the rest
-        float mx = sa[0];
+        // softmax over the pair's L*P logits: a producer lane holds LPAIRS of them, the group the rest
+        float mxl = sa[0];
 #pragma unroll
-        for (int i = 1; i < LPAIRS; ++i) mx = fmaxf(mx, sa[i]);
-        mx = fmaxf(mx, __shfl_xor(mx, 1));
-        mx = fmaxf(mx, __shfl_xor(mx, 2));
-        mx = fmaxf(mx, __shfl_xor(mx, 4));
-        float sum = 0.f;
+        for (int i = 1; i < LPAIRS; ++i) mxl = fmaxf(mxl, sa[i]);
+        const float mx = g.group_max(mxl);
+        float suml = 0.f;
 #pragma unroll
         for (int i = 0; i < LPAIRS; ++i) {
             sa[i] = have[i] ? __expf(sa[i] - mx) : 0.f;
-            sum += sa[i];
+            suml += sa[i];
         }
-        sum += __shfl_xor(sum, 1);
-        sum += __shfl_xor(sum, 2);
-        sum += __shfl_xor(sum, 4);
+        const float sum = g.group_sum(suml);
 #pragma unroll
         for (int i = 0; i < LPAIRS; ++i) {
             sa[i] = sa[i] / sum;
             const int ml = have[i] ? 2 * i + which : 0;
             const float *rp = da.fa.ref + (bqc * L + ml) * da.fa.ref_dim;
-            if (da.fa.ref_dim == 2) {
-                sx[i] = rp[0] + sx[i] / (float)s_tab[ml];                         // x / H_l (as written)
-                sy[i] = rp[1] + sy[i] / (float)s_tab[TF_MSDA_MAX_LEVELS + ml];    // y / W_l
-            } else {
-                sx[i] = rp[0] + sx[i] / (float)PT * rp[2] * 0.5f;
-                sy[i] = rp[1] + sy[i] / (float)PT * rp[3] * 0.5f;
-            }
+            const float2 xy = fused_location(rp, da.fa.ref_dim, make_float2(sx[i], sy[i]), (float)s_tab[ml],
+                                             (float)s_tab[TF_MSDA_MAX_LEVELS + ml], 1.f / (float)PT);
+            sx[i] = xy.x;
+            sy[i] = xy.y;
         }
     }
 
     const unsigned rowbytes = (unsigned)(M * D) * 4u;
     const unsigned head_base = (unsigned)((((long long)b * da.S * M + head) * D) * 4);
-    const unsigned dvb = (unsigned)dv * 16u;
+    const unsigned dvb = (unsigned)dv * 16u;   // <= 128: kOobBase + dvb stays out of range -> hardware zero
     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<float *>(da.value), 0, da.value_bytes, 0x00020000);
+    const int xbase = g.xbase();
 
     f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -540,6 +549,8 @@ msda_fwd_f32_direct(const DirectArgs da, const LevelTable lt, const int64_t *__r
         const int ml = have[i] ? 2 * i + which : 0;
         const int H = s_tab[ml], W = s_tab[TF_MSDA_MAX_LEVELS + ml];
         const unsigned lvl_base = head_base + (unsigned)s_tab[2 * TF_MSDA_MAX_LEVELS + ml] * rowbytes;
+        // pixel_point / point_corners (msda_point.h) written out: through the helpers msda_fwd_f32_direct<2, plain> takes 73
+        // VGPRs instead of 71 and drops from 7 to 6 waves per SIMD (tests/test_msda_point_single_definition.py lists the site)
         const float Wf = (float)W, Hf = (float)H;
         const float xr = __builtin_fmaf(sx[i], Wf, -0.5f);   // cuh:227-228, single rounding
         const float yr = __builtin_fmaf(sy[i], Hf, -0.5f);
@@ -559,18 +570,18 @@ msda_fwd_f32_direct(const DirectArgs da, const LevelTable lt, const int64_t *__r
         const float a = in ? sa[i] : 0.f;
         const float pw0 = gy * gx * a, pw1 = gy * fx * a, pw2 = fy * gx * a, pw3 = fy * fx * a;
 
-        // publish: LDS operations of a wave execute in order, so a wave-scope fence is all the
+        // publish (the producer lanes): LDS operations of a wave execute in order, so a wave-scope fence is all the
         // synchronisation there is (it also orders the previous level pair's reads before this write)
-        const int lane = threadIdx.x & 63;
-        const int xbase = (threadIdx.x >> 6) * 72 + (lane >> 3) * 9;   // slot of lane 0 of this group
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        s_xo[xbase + dv] = u32x4_t{(unsigned)po0, (unsigned)po1, (unsigned)po2, (unsigned)po3};
-        s_xw[xbase + dv] = f32x4_t{pw0, pw1, pw2, pw3};
+        if (producer) {
+            s_xo[xbase + dv] = u32x4_t{(unsigned)po0, (unsigned)po1, (unsigned)po2, (unsigned)po3};
+            s_xw[xbase + dv] = f32x4_t{pw0, pw1, pw2, pw3};
+        }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
 
         // consume: the points of one level (produced by lanes 4*ll .. 4*ll+3 of the group) at a time,
-        // 16 row gathers in flight per lane
+        // 16 row gathers (16 bytes each) in flight per lane
 #pragma unroll
         for (int ll = 0; ll < 2; ++ll) {
             if (2 * i + ll >= L) break;   // uniform
@@ -597,164 +608,18 @@ msda_fwd_f32_direct(const DirectArgs da, const LevelTable lt, const int64_t *__r
     if (live) *reinterpret_cast<f32x4_t *>(da.out + pair * D + dv * 4) = acc;
 }
 
-// ---------------------------------------------------------------------------------------------
-// forward, fp32, D == 36 (hidden 288: cfg 4), P == 4, L <= 8: msda_fwd_f32_direct's mapping with 9 lanes per pair
-// ---------------------------------------------------------------------------------------------
-// The decoder calls of the `multi_frame` model (D = 36, L = 8: two frames x 4 levels, 500 + 300 queries) ran
-// msda_fwd_f32_buf: every lane repeats the tap arithmetic (965 vector instructions per wave against 380 in
-// msda_fwd_f32_direct) behind a staging prologue.  This kernel keeps `direct`'s structure -- points fetched straight
-// into registers, the tap arithmetic of a point computed once per pair and published through a per-wave LDS
-// exchange, 16 row gathers in flight per lane -- for 144-byte rows: a (query, head) pair is served by NINE lanes
-// (4 channels each), seven pairs per wave (lane 63 idles), 28 pairs per 256-thread workgroup.  Lanes 0-7 of a group
-// produce (lanes 0-3: the points of level 2i, lanes 4-7: those of level 2i + 1), all nine consume.  The groups are
-// not aligned to DPP rows, so the softmax statistics of the fused entry go through wave shuffles (ds_bpermute).
-// OPT-IN until it has been timed on hardware: tf_msda_set_option("direct9", 1) / TF_MSDA_DIRECT9=1.
-template <int LPAIRS, bool FUSED>   // LPAIRS = ceil(L / 2)
+template <int LPAIRS, bool FUSED>
+__global__ void __launch_bounds__(kThreads, 4)
+msda_fwd_f32_direct(const DirectArgs da, const LevelTable lt, const int64_t *__restrict__ dshapes)
+{
+    direct_body<DirectGeom8, LPAIRS, FUSED>(da, lt, dshapes);
+}
+
+template <int LPAIRS, bool FUSED>
 __global__ void __launch_bounds__(kThreads, 4)
 msda_fwd_f32_direct9(const DirectArgs da, const LevelTable lt, const int64_t *__restrict__ dshapes)
 {
-    constexpr int PT = 4, D = 36, GL = 9, GPW = 7;   // lanes per pair, pairs per wave
-    __shared__ int s_tab[3 * TF_MSDA_MAX_LEVELS];
-    __shared__ u32x4_t s_xo[(kThreads / 64) * 72];   // per wave: 7 groups x 9 slots (8 used) + padding
-    __shared__ f32x4_t s_xw[(kThreads / 64) * 72];
-    const int L = da.L, M = da.M, LP = L * PT;
-    fill_level_table(s_tab, lt, dshapes, L);
-
-    const int head = blockIdx.x % M;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int grp = lane / GL, dv = lane - grp * GL;          // lane 63: grp 7, dv 0 (idle)
-    const long long bq = (long long)(blockIdx.x / M) * ((kThreads / 64) * GPW) + wave * GPW + grp;
-    const bool live = grp < GPW && bq < da.nlq;
-    const bool producer = dv < 8 && grp < GPW;
-    const int sub = dv & 3, which = (dv >> 2) & 1;
-    const long long bqc = live ? bq : 0;
-    const long long pair = bqc * M + head;
-    const int b = (int)(bqc / da.Lq);
-
-    // ---- this lane's sampling points: (level 2i + which, point sub) for i < LPAIRS (lanes 0-7 of a group) ----
-    float sx[LPAIRS], sy[LPAIRS], sa[LPAIRS];
-    bool have[LPAIRS];
-#pragma unroll
-    for (int i = 0; i < LPAIRS; ++i) {
-        const int ml = 2 * i + which;
-        have[i] = producer && ml < L;
-        const int s = (have[i] ? ml : 0) * PT + sub;
-        if constexpr (!FUSED) {
-            const float2 xy = *reinterpret_cast<const float2 *>(da.loc + (pair * LP + s) * 2);
-            sx[i] = xy.x;
-            sy[i] = xy.y;
-            sa[i] = da.attn[pair * LP + s];
-        } else {
-            const float *row = da.fa.qproj + bqc * da.fa.ld;
-            const float2 off = *reinterpret_cast<const float2 *>(row + da.fa.off_col + (head * LP + s) * 2);
-            sx[i] = off.x;
-            sy[i] = off.y;
-            sa[i] = have[i] ? row[da.fa.logit_col + head * LP + s] : -__builtin_inff();
-        }
-    }
-    __syncthreads();   // level table
-
-    if constexpr (FUSED) {
-#pragma clang fp contract(off)   // keep the reference's operation order (no fused multiply-add)
-        // softmax over the pair's L*P logits: the eight producer lanes of the group hold LPAIRS of them each
-        const int gbase = grp * GL;
-        float mxl = sa[0];
-#pragma unroll
-        for (int i = 1; i < LPAIRS; ++i) mxl = fmaxf(mxl, sa[i]);
-        float mx = -__builtin_inff();
-#pragma unroll
-        for (int k = 0; k < 8; ++k) mx = fmaxf(mx, __shfl(mxl, gbase + k));
-        float suml = 0.f;
-#pragma unroll
-        for (int i = 0; i < LPAIRS; ++i) {
-            sa[i] = have[i] ? __expf(sa[i] - mx) : 0.f;
-            suml += sa[i];
-        }
-        float sum = 0.f;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) sum += __shfl(suml, gbase + k);
-#pragma unroll
-        for (int i = 0; i < LPAIRS; ++i) {
-            sa[i] = sa[i] / sum;
-            const int ml = have[i] ? 2 * i + which : 0;
-            const float *rp = da.fa.ref + (bqc * L + ml) * da.fa.ref_dim;
-            if (da.fa.ref_dim == 2) {
-                sx[i] = rp[0] + sx[i] / (float)s_tab[ml];                         // x / H_l (as written)
-                sy[i] = rp[1] + sy[i] / (float)s_tab[TF_MSDA_MAX_LEVELS + ml];    // y / W_l
-            } else {
-                sx[i] = rp[0] + sx[i] / (float)PT * rp[2] * 0.5f;
-                sy[i] = rp[1] + sy[i] / (float)PT * rp[3] * 0.5f;
-            }
-        }
-    }
-
-    const unsigned rowbytes = (unsigned)(M * D) * 4u;
-    const unsigned head_base = (unsigned)((((long long)b * da.S * M + head) * D) * 4);
-    const unsigned dvb = (unsigned)dv * 16u;   // <= 128: kOobBase + dvb stays out of range
-    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float *>(da.value), 0, da.value_bytes, 0x00020000);
-    // slot of lane 0 of this group; lane 63 reads along with group 6 (valid offsets, results never stored)
-    const int xbase = wave * 72 + (grp < GPW ? grp : GPW - 1) * GL;
-
-    f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int i = 0; i < LPAIRS; ++i) {
-        // produce: taps of this lane's point of the level pair (2i, 2i+1)
-        const int ml = have[i] ? 2 * i + which : 0;
-        const int H = s_tab[ml], W = s_tab[TF_MSDA_MAX_LEVELS + ml];
-        const unsigned lvl_base = head_base + (unsigned)s_tab[2 * TF_MSDA_MAX_LEVELS + ml] * rowbytes;
-        const float Wf = (float)W, Hf = (float)H;
-        const float xr = __builtin_fmaf(sx[i], Wf, -0.5f);   // cuh:227-228, single rounding
-        const float yr = __builtin_fmaf(sy[i], Hf, -0.5f);
-        const bool in = have[i] && live && (yr > -1.f) && (xr > -1.f) && (yr < Hf) && (xr < Wf);
-        const float x = in ? xr : 0.f, y = in ? yr : 0.f;
-        const float xf = __builtin_floorf(x), yf = __builtin_floorf(y);
-        const float fx = x - xf, fy = y - yf, gx = 1.f - fx, gy = 1.f - fy;
-        const int x0 = (int)xf, y0 = (int)yf;
-        const bool kx0 = in && (x0 >= 0), kx1 = in && (x0 + 1 <= W - 1);
-        const bool ky0 = in && (y0 >= 0), ky1 = in && (y0 + 1 <= H - 1);
-        const int r0 = y0 * W + x0;
-        const int po0 = (int)((ky0 && kx0) ? lvl_base + (unsigned)r0 * rowbytes : kOobBase);
-        const int po1 = (int)((ky0 && kx1) ? lvl_base + (unsigned)(r0 + 1) * rowbytes : kOobBase);
-        const int po2 = (int)((ky1 && kx0) ? lvl_base + (unsigned)(r0 + W) * rowbytes : kOobBase);
-        const int po3 = (int)((ky1 && kx1) ? lvl_base + (unsigned)(r0 + W + 1) * rowbytes : kOobBase);
-        const float a = in ? sa[i] : 0.f;
-        const float pw0 = gy * gx * a, pw1 = gy * fx * a, pw2 = fy * gx * a, pw3 = fy * fx * a;
-
-        // publish (lanes 0-7 of the seven groups): wave-scope ordering as in `direct`
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        if (producer) {
-            s_xo[xbase + dv] = u32x4_t{(unsigned)po0, (unsigned)po1, (unsigned)po2, (unsigned)po3};
-            s_xw[xbase + dv] = f32x4_t{pw0, pw1, pw2, pw3};
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-
-        // consume: one level at a time, 16 row gathers (16 bytes each) in flight per lane
-#pragma unroll
-        for (int ll = 0; ll < 2; ++ll) {
-            if (2 * i + ll >= L) break;   // uniform
-            u32x4_t v[4][4];
-            f32x4_t w[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const u32x4_t o = s_xo[xbase + ll * 4 + k];
-                w[k] = s_xw[xbase + ll * 4 + k];
-                v[k][0] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, o.x + dvb, 0, 0);
-                v[k][1] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, o.y + dvb, 0, 0);
-                v[k][2] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, o.z + dvb, 0, 0);
-                v[k][3] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, o.w + dvb, 0, 0);
-            }
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                acc += __builtin_bit_cast(f32x4_t, v[k][0]) * w[k].x;
-                acc += __builtin_bit_cast(f32x4_t, v[k][1]) * w[k].y;
-                acc += __builtin_bit_cast(f32x4_t, v[k][2]) * w[k].z;
-                acc += __builtin_bit_cast(f32x4_t, v[k][3]) * w[k].w;
-            }
-        }
-    }
-    if (live) *reinterpret_cast<f32x4_t *>(da.out + pair * D + dv * 4) = acc;
+    direct_body<DirectGeom9, LPAIRS, FUSED>(da, lt, dshapes);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -949,11 +814,9 @@ msda_bwd_f32_sorted2(const BwdSortArgs ba, const LevelTable lt, const WinGeom wg
             sx[i][ps] = xy.x;
             sy[i][ps] = xy.y;
             sa[i][ps] = ba.attn[pi];
-            const float xr = __builtin_fmaf(xy.x, Wf, -0.5f);
-            const float yr = __builtin_fmaf(xy.y, Hf, -0.5f);
-            const bool in = live[ps] && have && (yr > -1.f) && (xr > -1.f) && (yr < Hf) && (xr < Wf);
-            const int x0 = (int)__builtin_floorf(in ? xr : 0.f), y0 = (int)__builtin_floorf(in ? yr : 0.f);
-            if (in) {
+            const PixelPoint<float> pt = pixel_point(xy.x, xy.y, Wf, Hf, live[ps] && have);
+            const int x0 = pt.x0, y0 = pt.y0;
+            if (pt.in) {
                 mnx = min(mnx, x0 >= 0 ? x0 : x0 + 1);
                 mxx = max(mxx, (x0 + 1 <= W - 1) ? x0 + 1 : x0);
                 mny = min(mny, y0 >= 0 ? y0 : y0 + 1);
@@ -1043,18 +906,13 @@ msda_bwd_f32_sorted2(const BwdSortArgs ba, const LevelTable lt, const WinGeom wg
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // the previous round's reads are done
             if (owner) {
                 const float a = sa[l >> 1][ps];
-                const float xr = __builtin_fmaf(sx[l >> 1][ps], Wf, -0.5f);   // cuh:350-351
-                const float yr = __builtin_fmaf(sy[l >> 1][ps], Hf, -0.5f);
-                const bool in = live[ps] && (yr > -1.f) && (xr > -1.f) && (yr < Hf) && (xr < Wf);   // cuh:359
-                const float x = in ? xr : 0.f, y = in ? yr : 0.f;
-                const float xf = __builtin_floorf(x), yf = __builtin_floorf(y);
-                const float fx = x - xf, fy = y - yf, gx = 1.f - fx, gy = 1.f - fy;
-                const int x0 = (int)xf, y0 = (int)yf;
-                const bool kx0 = in && (x0 >= 0), kx1 = in && (x0 + 1 <= W - 1);
-                const bool ky0 = in && (y0 >= 0), ky1 = in && (y0 + 1 <= H - 1);
-                const bool kt[4] = {ky0 && kx0, ky0 && kx1, ky1 && kx0, ky1 && kx1};
-                const int r0 = y0 * W + x0;
-                const unsigned t1 = lvl_base + (unsigned)r0 * rowbytes, t2 = t1 + rowbytes;
+                const PixelPoint<float> pt = pixel_point(sx[l >> 1][ps], sy[l >> 1][ps], Wf, Hf, live[ps]);   // cuh:350-351, :359
+                const float fx = pt.fx, fy = pt.fy, gx = pt.gx, gy = pt.gy;
+                const int x0 = pt.x0, y0 = pt.y0;
+                const bool in = pt.in;
+                const PointCorners c = point_corners(x0, y0, W, H, in);
+                const bool kt[4] = {c.ky0 && c.kx0, c.ky0 && c.kx1, c.ky1 && c.kx0, c.ky1 && c.kx1};
+                const unsigned t1 = lvl_base + (unsigned)c.r0 * rowbytes, t2 = t1 + rowbytes;
                 const unsigned t3 = t1 + (unsigned)W * rowbytes, t4 = t3 + rowbytes;
                 const float w[4] = {gy * gx, gy * fx, fy * gx, fy * fx};
                 xch[sub * 3 + 0] = u32x4_t{kt[0] ? t1 : kOobBase, kt[1] ? t2 : kOobBase, kt[2] ? t3 : kOobBase,
@@ -1442,18 +1300,11 @@ msda_bwd_f32_buf(const float *__restrict__ value, unsigned value_bytes,
                 const int s = l * PT + p;
                 const float2 xy = sl[s];
                 const float a = sa[s];
-                const float xr = __builtin_fmaf(xy.x, Wf, -0.5f);   // cuh:350-351
-                const float yr = __builtin_fmaf(xy.y, Hf, -0.5f);
-                const bool in = (yr > -1.f) && (xr > -1.f) && (yr < Hf) && (xr < Wf);  // cuh:359
-                const float x = in ? xr : 0.f, y = in ? yr : 0.f;
-                const float xf = __builtin_floorf(x), yf = __builtin_floorf(y);
-                const float fx = x - xf, fy = y - yf, gx = 1.f - fx, gy = 1.f - fy;
-                const int x0 = (int)xf, y0 = (int)yf;
-                const bool kx0 = in && (x0 >= 0), kx1 = in && (x0 + 1 <= W - 1);
-                const bool ky0 = in && (y0 >= 0), ky1 = in && (y0 + 1 <= H - 1);
-                const int r0 = y0 * W + x0;
-                const bool k1 = ky0 && kx0, k2 = ky0 && kx1, k3 = ky1 && kx0, k4 = ky1 && kx1;
-                const unsigned t1 = lvl_base + (unsigned)r0 * rowbytes;        // row byte offsets
+                const PixelPoint<float> pt = pixel_point(xy.x, xy.y, Wf, Hf, true);   // cuh:350-351, :359
+                const float fx = pt.fx, fy = pt.fy, gx = pt.gx, gy = pt.gy;
+                const PointCorners c = point_corners(pt.x0, pt.y0, W, H, pt.in);
+                const bool k1 = c.ky0 && c.kx0, k2 = c.ky0 && c.kx1, k3 = c.ky1 && c.kx0, k4 = c.ky1 && c.kx1;
+                const unsigned t1 = lvl_base + (unsigned)c.r0 * rowbytes;      // row byte offsets
                 const unsigned t2 = t1 + rowbytes;
                 const unsigned t3 = t1 + (unsigned)W * rowbytes;
                 const unsigned t4 = t3 + rowbytes;

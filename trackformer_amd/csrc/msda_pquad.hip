@@ -49,6 +49,7 @@
 #include "tf_msda.h"
 #include "msda_common.h"
 #include "msda_dispatch.h"
+#include "msda_point.h"
 #include "msda_quad_geom.h"
 
 namespace {
@@ -414,10 +415,9 @@ msda_fwd_f32_pquad(const DirectArgs da, const LevelTable lt, const PquadGeom pg)
             const float Wf = (float)Ws[l], Hf = (float)Hs[l];
 #pragma unroll
             for (int ps = 0; ps < NPASS; ++ps) {
-                const float xr = __builtin_fmaf(p.sx[ps][l], Wf, -0.5f);
-                const float yr = __builtin_fmaf(p.sy[ps][l], Hf, -0.5f);
-                const bool in = p.live[ps] && (yr > -1.f) && (xr > -1.f) && (yr < Hf) && (xr < Wf);
-                const int x0 = (int)__builtin_floorf(in ? xr : 0.f), y0 = (int)__builtin_floorf(in ? yr : 0.f);
+                const PixelPoint<float> pt = pixel_point(p.sx[ps][l], p.sy[ps][l], Wf, Hf, p.live[ps]);
+                const int x0 = pt.x0, y0 = pt.y0;
+                const bool in = pt.in;
                 mnx = min(mnx, in ? x0 : INT_MAX);
                 mxx = max(mxx, in ? x0 : INT_MIN);
                 mny = min(mny, in ? y0 : INT_MAX);
@@ -652,13 +652,10 @@ msda_fwd_f32_pquad(const DirectArgs da, const LevelTable lt, const PquadGeom pg)
             if (ps * PAIRS >= cur.nq) return;            // uniform
             const int H = Hs[l], W = Ws[l];
             const float Wf = (float)W, Hf = (float)H;
-            const float xr = __builtin_fmaf(cur.sx[ps][l], Wf, -0.5f);   // cuh:227-228 with one rounding (see make_tap, msda_hip.hip)
-            const float yr = __builtin_fmaf(cur.sy[ps][l], Hf, -0.5f);
-            const bool in = cur.live[ps] && (yr > -1.f) && (xr > -1.f) && (yr < Hf) && (xr < Wf);
-            const float x = in ? xr : 0.f, y = in ? yr : 0.f;
-            const float xf = __builtin_floorf(x), yf = __builtin_floorf(y);
-            const float fx = x - xf, fy = y - yf, gx = 1.f - fx, gy = 1.f - fy;
-            const int x0 = (int)xf, y0 = (int)yf;
+            const PixelPoint<float> pt = pixel_point(cur.sx[ps][l], cur.sy[ps][l], Wf, Hf, cur.live[ps]);
+            const float fx = pt.fx, fy = pt.fy, gx = pt.gx, gy = pt.gy;
+            const int x0 = pt.x0, y0 = pt.y0;
+            const bool in = pt.in;
             const float a = in ? cur.sa[ps][l] : 0.f;
             const float w[4] = {gy * gx * a, gy * fx * a, fy * gx * a, fy * fx * a};
             bool need_global = in;
@@ -685,15 +682,13 @@ msda_fwd_f32_pquad(const DirectArgs da, const LevelTable lt, const PquadGeom pg)
                 if constexpr ((kPqAblate & 32) != 0) return;
                 if (!__any(need_global)) return;   // wave-uniform: no point of this wave left its window
             }
-            const bool kx0 = need_global && (x0 >= 0), kx1 = need_global && (x0 + 1 <= W - 1);
-            const bool ky0 = (y0 >= 0), ky1 = (y0 + 1 <= H - 1);
-            const int r0 = y0 * W + x0;
+            const PointCorners c = point_corners(x0, y0, W, H, need_global);
             const unsigned lvl_base = glvl[l];
             // staged / invalid taps: kOobBase + (lane offset < 128) is still out of range -> hardware zero
-            const unsigned g[4] = {(ky0 && kx0) ? lvl_base + (unsigned)r0 * rowbytes : kOobBase,
-                                   (ky0 && kx1) ? lvl_base + (unsigned)(r0 + 1) * rowbytes : kOobBase,
-                                   (ky1 && kx0) ? lvl_base + (unsigned)(r0 + W) * rowbytes : kOobBase,
-                                   (ky1 && kx1) ? lvl_base + (unsigned)(r0 + W + 1) * rowbytes : kOobBase};
+            const unsigned g[4] = {(c.ky0 && c.kx0) ? lvl_base + (unsigned)c.r0 * rowbytes : kOobBase,
+                                   (c.ky0 && c.kx1) ? lvl_base + (unsigned)(c.r0 + 1) * rowbytes : kOobBase,
+                                   (c.ky1 && c.kx0) ? lvl_base + (unsigned)c.r1 * rowbytes : kOobBase,
+                                   (c.ky1 && c.kx1) ? lvl_base + (unsigned)(c.r1 + 1) * rowbytes : kOobBase};
             if constexpr (!D36) {
                 quad_taps_global<0>(rsrc, g, w, rbA, rbB, accA[ps], accB[ps]);
                 quad_taps_global<1>(rsrc, g, w, rbA, rbB, accA[ps], accB[ps]);

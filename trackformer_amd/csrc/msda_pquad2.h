@@ -440,7 +440,9 @@ msda_fwd_f32_pquad2(const DirectArgs da, const LevelTable lt, const PquadGeom pg
             }
 #pragma unroll
             for (int k = 0; k < PT; ++k) {
-                const float xr = __builtin_fmaf(sx[k], my_Wf, -0.5f);   // cuh:227-228 with one rounding (see make_tap, msda_hip.hip)
+                // pixel_point (msda_point.h) written out: through the helper the fused instantiations take 4 to 5 more VGPRs and
+                // the conflict-free ones spill 16 / 32 bytes (tests/test_msda_point_single_definition.py lists the site)
+                const float xr = __builtin_fmaf(sx[k], my_Wf, -0.5f);   // cuh:227-228 with one rounding
                 const float yr = __builtin_fmaf(sy[k], my_Hf, -0.5f);
                 const bool in = live[ps] && lvalid && (yr > -1.f) && (xr > -1.f) && (yr < my_Hf) && (xr < my_Wf);
                 const float x = in ? xr : 0.f, y = in ? yr : 0.f;
