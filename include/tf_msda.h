@@ -65,7 +65,8 @@ int tf_msda_abi_version(void);
 /* Human-readable text for a tf_msda_status. Never NULL. */
 const char *tf_msda_strerror(int status);
 
-/* hipError_t (as int) of the most recent failing HIP call on this thread, 0 if none. */
+/* hipError_t (as int) of the most recent failing HIP call on this thread, 0 if none.  Covers every entry point of this header
+ * and of tf_fused.h: whichever returned TF_MSDA_ERR_LAUNCH last on this thread stored its code here. */
 int tf_msda_last_hip_error(void);
 
 /*

@@ -7,6 +7,7 @@ import ctypes
 import numpy as np
 
 from tests.emu import build_emu
+from trackformer_amd import _cabi
 
 _lib = None
 
@@ -27,81 +28,11 @@ def lib():
     so = build_emu.build()
     if so is None:
         raise RuntimeError("no host clang++ to build the emulated library with")
-    L = ctypes.CDLL(so)
-    vp, ci = ctypes.c_void_p, ctypes.c_int
-    L.tf_msda_set_tiled.restype = ci
-    L.tf_msda_set_tiled.argtypes = [ci]
-    L.tf_msda_set_option.restype = ci
-    L.tf_msda_set_option.argtypes = [ctypes.c_char_p, ci]
-    for suf in ("f32", "f64"):
-        for tail in ("", "_dshapes"):
-            f = getattr(L, "tf_msda_forward_%s%s" % (suf, tail))
-            f.restype = ci
-            f.argtypes = [vp] * 5 + [ci] * 7 + [vp]
-            b = getattr(L, "tf_msda_backward_%s%s" % (suf, tail))
-            b.restype = ci
-            b.argtypes = [vp] * 8 + [ci] * 7 + [vp]
-    L.tf_msda_forward_fused_f32.restype = ci
-    L.tf_msda_forward_fused_f32.argtypes = [vp, vp, vp, ci, vp, ci, ci, ci, vp] + [ci] * 7 + [vp]
-    L.tf_bias_act_f32.restype = ci
-    L.tf_bias_act_f32.argtypes = [vp, vp, vp, ctypes.c_int64, ci, ci, vp]
-    L.tf_add_layernorm_f32.restype = ci
-    L.tf_add_layernorm_f32.argtypes = [vp, vp, vp, vp, vp, ctypes.c_int64, ci, ctypes.c_float, vp]
-    L.tf_stem_conv7x7_f32.restype = ci
-    L.tf_stem_conv7x7_f32.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, vp]
-    L.tf_bias_relu_maxpool_f32.restype = ci
-    L.tf_bias_relu_maxpool_f32.argtypes = [vp, vp, vp, ci, ci, ci, ci, vp]
-    L.tf_box_refine_f32.restype = ci
-    L.tf_box_refine_f32.argtypes = [vp, vp, vp, ctypes.c_int64, ci, ctypes.c_float, vp]
-    L.tf_postprocess_pack_f32.restype = ci
-    L.tf_postprocess_pack_f32.argtypes = [vp, vp, vp, ctypes.c_int64, ci, ctypes.c_float, ctypes.c_float, ci, vp]
-    L.tf_groupnorm_stats_nhwc_f32.restype = ci
-    L.tf_groupnorm_stats_nhwc_f32.argtypes = [vp, vp, ci, ci, ci, ci, ctypes.c_int64, vp]
-    L.tf_conv3x3_merge_packed_f32.restype = ci
-    L.tf_conv3x3_merge_packed_f32.argtypes = [vp, vp, vp, vp, vp, ci, ctypes.c_float, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, vp]
-    L.tf_mask_label_map_f32.restype = ci
-    L.tf_mask_label_map_f32.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, ctypes.c_float, vp]
-    L.tf_upsample_add_nhwc_f32.restype = ci
-    L.tf_upsample_add_nhwc_f32.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp]
-    L.tf_groupnorm_relu_conv3x3_c1_nhwc_f32.restype = ci
-    L.tf_groupnorm_relu_conv3x3_c1_nhwc_f32.argtypes = [vp, vp, vp, vp, ctypes.c_float, vp, vp, ci, ci, ci, ci, ci, ctypes.c_float, vp]
-    for fn in (L.tf_groupnorm_nhwc_f32, L.tf_groupnorm_relu_nhwc_f32):
-        fn.restype = ci
-        fn.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, ctypes.c_float, ctypes.c_int64, ctypes.c_int64, vp]
-    L.tf_linear_res_ln_f32.restype = ci
-    L.tf_linear_res_ln_f32.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_float, vp, ctypes.c_int64, ci, ci, ci, vp]
-    L.tf_ffn_fused_f32.restype = ci
-    L.tf_ffn_fused_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_float, vp, ctypes.c_int64, ci, ci, ci, vp]
-    L.tf_linear_split_add_f32.restype = ci
-    L.tf_linear_split_add_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_int64, ci, ci, vp]
-    L.tf_linear_split_f32.restype = ci
-    L.tf_linear_split_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, ctypes.c_int64, ci, ci, ci, vp]
-    L.tf_linear_split_res_f32.restype = ci
-    L.tf_linear_split_res_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_int64, ci, ci, ci, vp]
-    L.tf_conv3x3_splitk_f32.restype = ci
-    L.tf_conv3x3_splitk_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, vp]
-    L.tf_conv3x3_split_f32.restype = ci
-    L.tf_conv3x3_split_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp] + [ci] * 7 + [vp]
-    L.tf_conv1x1_splitk_f32.restype = ci
-    L.tf_conv1x1_splitk_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, vp]
-    L.tf_conv1x1_strided_split_f32.restype = ci
-    L.tf_conv1x1_strided_split_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp] + [ci] * 7 + [vp]
-    L.tf_linear_packed_bytes.restype = ctypes.c_int64
-    L.tf_linear_packed_bytes.argtypes = [ci, ci, ci]
-    L.tf_linear_pack_weight_f32.restype = ci
-    L.tf_linear_pack_weight_f32.argtypes = [vp, vp, ci, ci, ci, vp]
-    L.tf_linear_packed_f32.restype = ci
-    L.tf_linear_packed_f32.argtypes = [vp, vp, vp, vp, vp, ctypes.c_int64, ci, ci, ci, ci, vp]
-    L.tf_conv_packed_f32.restype = ci
-    L.tf_conv_packed_f32.argtypes = [vp, vp, vp, vp, vp, vp] + [ci] * 10 + [vp]
-    L.tf_mha_core_f32.restype = ci
-    L.tf_mha_core_f32.argtypes = [vp, vp, vp, vp, vp] + [ci] * 9 + [ctypes.c_float, vp]
-    L.tf_msda_last_kernel.restype = ctypes.c_char_p
-    L.tf_msda_last_kernel.argtypes = []
+    L = _cabi.bind(ctypes.CDLL(so))   # the same ABI, read from the same headers; by hand only what they do not declare
     L.hipemu_get_stats.restype = None
-    L.hipemu_get_stats.argtypes = [vp]
+    L.hipemu_get_stats.argtypes = [ctypes.c_void_p]
     L.hipemu_reset_stats.restype = None
-    L.hipemu_num_cus.restype = ci
+    L.hipemu_num_cus.restype = ctypes.c_int
     _lib = L
     return L
 

@@ -5,8 +5,6 @@ of fused.set_attention_training that needs no GPU.
 
 Every operand lives in a buffer with NaN in the gaps between its rows; every output in one with a canary in the gaps and in three rows
 behind the last, checked unchanged: a store outside the tensor fails the test."""
-import ctypes
-
 import numpy as np
 import pytest
 import torch
@@ -26,15 +24,7 @@ PS = [None, 0.1, 0.5]
 
 
 def _lib():
-    L = emu_lib.lib()
-    if not getattr(L, "_attention_train_bound", False):
-        vp, ci, cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
-        L.tf_mha_core_train_f32.restype = ci
-        L.tf_mha_core_train_f32.argtypes = [vp] * 7 + [cf] + [ci] * 9 + [cf, vp]
-        L.tf_mha_core_bwd_f32.restype = ci
-        L.tf_mha_core_bwd_f32.argtypes = [vp] * 8 + [cf] + [vp] * 3 + [ci] * 13 + [cf, vp]
-        L._attention_train_bound = True
-    return L
+    return emu_lib.lib()   # bound from the headers (trackformer_amd._cabi.bind)
 
 
 def _rng(seed=SEED, offset=OFFSET):

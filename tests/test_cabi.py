@@ -1,4 +1,5 @@
-"""CPU: the C-ABI shared library loads and exports exactly what include/tf_msda.h declares;
+"""CPU: the C-ABI shared library loads and exports exactly what include/tf_msda.h and include/tf_fused.h declare, and the
+binding read from those headers (_cabi.signatures / bind) gives every function the types the prototypes state;
 argument validation works without a GPU (no compute is launched here)."""
 import ctypes
 import os
@@ -28,8 +29,83 @@ def _declared_symbols():
     return sorted(names)
 
 
-def test_header_and_binding_agree():
-    assert _declared_symbols() == sorted(_cabi.EXPORTED_SYMBOLS)
+def test_parser_finds_every_declared_name():
+    """The binder's parse against the cruder, independent list above: it cannot silently skip a prototype."""
+    assert sorted(_cabi.signatures()) == _declared_symbols()
+    assert sorted(_cabi.EXPORTED_SYMBOLS) == _declared_symbols()
+    assert len(set(_cabi.EXPORTED_SYMBOLS)) == len(_cabi.EXPORTED_SYMBOLS)
+
+
+_VP, _CI, _I64, _CF = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
+# Written by hand, one function of each kind: (restype, argtypes) as the hand-written binding had them.
+PINNED = {
+    "tf_msda_abi_version": (_CI, []),
+    "tf_msda_strerror": (ctypes.c_char_p, [_CI]),
+    "tf_msda_set_option": (_CI, [ctypes.c_char_p, _CI]),
+    "tf_msda_debug_trace_buffer": (None, [_VP]),
+    "tf_linear_packed_bytes": (_I64, [_CI, _CI, _CI]),
+    "tf_groupnorm_nhwc_f32": (_CI, [_VP, _VP, _VP, _VP, _VP, _CI, _CI, _CI, _CI, _CF, _I64, _I64, _VP]),
+    "tf_groupnorm_relu_conv3x3_c1_nhwc_f32": (_CI, [_VP, _VP, _VP, _VP, _CF, _VP, _VP, _CI, _CI, _CI, _CI, _CI, _CF, _VP]),
+    "tf_dropout_keep_u8": (_CI, [_VP, _CF, _I64, _I64, _VP, _VP]),
+    "tf_msda_backward_det_f32": (_CI, [_VP] * 9 + [_I64] + [_CI] * 7 + [_VP]),
+    "tf_linear_groups_f32": (_CI, [_VP, _VP, ctypes.POINTER(_cabi.ProjGroup), _CI, _I64, _CI, _CI, _VP]),
+    "tf_conv_packed_partials_f32": (_CI, [_VP, _VP, _VP, _VP] + [_CI] * 9 + [_VP, _VP]),
+    "tf_mha_core_bwd_f32": (_CI, [_VP] * 8 + [_CF] + [_VP] * 3 + [_CI] * 13 + [_CF, _VP]),
+}
+
+
+@pytest.mark.parametrize("name", sorted(PINNED))
+def test_pinned_signatures(name):
+    assert _cabi.signatures()[name] == PINNED[name]
+
+
+def test_parser_raises_on_a_type_outside_the_rule():
+    for text, func in (("int tf_x(long double v);", "tf_x"), ("int tf_y(int a, size_t n);", "tf_y"),
+                       ("unsigned tf_z(void);", "tf_z"), ("float *tf_w(int a);", "tf_w"), ("int tf_v(int);", "tf_v")):
+        with pytest.raises(TypeError, match=func):
+            _cabi.parse_prototypes(text)
+
+
+def test_parser_reads_a_prototype_over_three_lines_with_comments():
+    text = """
+    /* int tf_not_this(int a); */
+    // int tf_nor_this(int a);
+    int64_t tf_x(const float *a,   /* the input: tf_inner(1) */
+                 double *ws, int64_t n,  // a size
+                 float eps, const char *name, void *stream);
+    const char *tf_y(void);
+    """
+    assert _cabi.parse_prototypes(text) == {
+        "tf_x": (_I64, [_VP, _VP, _I64, _CF, ctypes.c_char_p, _VP]),
+        "tf_y": (ctypes.c_char_p, []),
+    }
+
+
+_FIELD_TYPES = {"int": ctypes.c_int, "int64_t": ctypes.c_int64}
+
+
+@pytest.mark.parametrize("c_name,cls", [("tf_proj_group", _cabi.ProjGroup), ("tf_gn_level", _cabi.GnLevel)])
+def test_structs_match_the_header(c_name, cls):
+    """Field names, order and C types of the hand-written ctypes.Structure against the typedef's body in tf_fused.h."""
+    text = open(os.path.join(REPO, "include", "tf_fused.h")).read()
+    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (c_name, c_name), text, flags=re.S).group(1)
+    fields = []
+    for decl in body.split(";"):
+        if not decl.strip():
+            continue
+        m = re.fullmatch(r"(.*[\s*])(\w+)", " ".join(decl.split()))
+        c_type = m.group(1).strip()
+        fields.append((m.group(2), ctypes.c_void_p if c_type.endswith("*") else _FIELD_TYPES[c_type]))
+    assert fields == list(cls._fields_)
+
+
+def test_every_declared_symbol_is_bound(lib):
+    """Nothing on the loaded library is left at ctypes' defaults (argtypes None, restype c_int by accident)."""
+    for name in _declared_symbols():
+        fn = getattr(lib, name)
+        restype, argtypes = _cabi.signatures()[name]
+        assert fn.argtypes is not None and list(fn.argtypes) == argtypes, name
+        assert fn.restype is restype, name
 
 
 def test_every_declared_symbol_is_exported(lib):

@@ -15,7 +15,7 @@ import torch
 import torch.nn.functional as F
 
 from tests import emu_lib
-from tests.test_linear_backward_cpu import ACT, TERMS, WEIGHT, _al, _bytes, _lib as _linear_lib
+from tests.test_linear_backward_cpu import ACT, TERMS, WEIGHT, _al, _bytes, _lib
 from tests.test_linear_backward_cpu import check_dgrad, check_wgrad, msplit, operands, pack, stats, wgrad as linear_wgrad  # noqa: F401
 
 emu = pytest.mark.skipif(not emu_lib.available(), reason="no host clang++ for the emulated library")
@@ -31,26 +31,6 @@ WGRAD_CASES = [
 ]
 # (nimg, h, w, cin, cout, stride)
 DGRAD_CASES = [(1, 1, 1, 4, 64, 1), (2, 5, 7, 36, 64, 1), (1, 9, 11, 128, 128, 1)]
-
-
-def bind(L):
-    """ctypes signatures of the three entry points on a library handle (the emulated one or libtf_msda.so)."""
-    if not getattr(L, "_conv_bwd_bound", False):
-        vp, ci, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
-        L.tf_conv3x3_wgrad_workspace_bytes.restype = i64
-        L.tf_conv3x3_wgrad_workspace_bytes.argtypes = [ci] * 6
-        L.tf_conv3x3_wgrad_split_f32.restype = ci
-        L.tf_conv3x3_wgrad_split_f32.argtypes = [vp, vp, vp, vp, vp, vp, i64] + [ci] * 7 + [vp]
-        L.tf_conv3x3_dgrad_packed_f32.restype = ci
-        L.tf_conv3x3_dgrad_packed_f32.argtypes = [vp, vp, vp, vp, vp] + [ci] * 7 + [vp]
-        L.tf_linear_dgrad_splitk_packed_f32.restype = ci
-        L.tf_linear_dgrad_splitk_packed_f32.argtypes = [vp, vp, vp, vp, vp, ci, i64, ci, ci, ci, vp]
-        L._conv_bwd_bound = True
-    return L
-
-
-def _lib():
-    return bind(_linear_lib())
 
 
 def out_size(n, stride):

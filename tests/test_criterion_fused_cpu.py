@@ -1,8 +1,6 @@
 """CPU: the fused set criterion and the matching cost (include/tf_fused.h: THE SET CRITERION AND THE MATCHING COST;
 trackformer_amd/csrc/criterion.h) on the emulated library -- the kernels' own source under the SIMT emulator -- against float64 with the
 yardstick of tests/util_criterion_fused.py, the yardstick's own self-tests, and the host logic of the two routes that needs no GPU."""
-import ctypes
-
 import numpy as np
 import pytest
 import torch
@@ -18,17 +16,7 @@ GUARD = 3            # canary rows behind every output
 
 
 def _lib():
-    L = emu_lib.lib()
-    if not getattr(L, "_criterion_bound", False):
-        vp, ci, i64, cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
-        L.tf_set_criterion_fwd_f32.restype = ci
-        L.tf_set_criterion_fwd_f32.argtypes = [vp] * 9 + [ci] * 5 + [cf, cf, cf, vp]
-        L.tf_set_criterion_bwd_f32.restype = ci
-        L.tf_set_criterion_bwd_f32.argtypes = [vp] * 8 + [ci] * 5 + [cf, cf, cf, vp]
-        L.tf_match_cost_f32.restype = ci
-        L.tf_match_cost_f32.argtypes = [vp] * 5 + [i64, ci, ci] + [cf] * 5 + [vp]
-        L._criterion_bound = True
-    return L
+    return emu_lib.lib()   # bound from the headers (trackformer_amd._cabi.bind)
 
 
 def _al(a, dt=np.float32):

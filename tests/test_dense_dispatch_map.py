@@ -99,9 +99,8 @@ def test_unknown_names_emulated():
 _CHILD = """
 import ctypes, sys
 from tests.emu import build_emu
-L = ctypes.CDLL(build_emu.build())
-L.tf_msda_set_option.restype = ctypes.c_int
-L.tf_msda_set_option.argtypes = [ctypes.c_char_p, ctypes.c_int]
+from trackformer_amd import _cabi
+L = _cabi.bind(ctypes.CDLL(build_emu.build()))
 print(" ".join("%s=%d" % (k, L.tf_msda_set_option(k.encode(), 1)) for k in sys.argv[1:]))
 """
 

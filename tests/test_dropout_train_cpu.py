@@ -25,23 +25,7 @@ SEED, OFFSET = 0x9E3779B97F4A7C15 - 2 ** 64, 0x7FEDCBA987654321   # both high ha
 
 
 def _lib():
-    L = emu_lib.lib()
-    if not getattr(L, "_dropout_bound", False):
-        vp, ci, i64, cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
-        L.tf_dropout_keep_u8.restype = ci
-        L.tf_dropout_keep_u8.argtypes = [vp, cf, i64, i64, vp, vp]
-        L.tf_add_dropout_layernorm_train_f32.restype = ci
-        L.tf_add_dropout_layernorm_train_f32.argtypes = [vp] * 5 + [cf, vp, vp, i64, ci, cf, vp]
-        L.tf_add_dropout_layernorm_bwd_f32.restype = ci
-        L.tf_add_dropout_layernorm_bwd_f32.argtypes = [vp] * 6 + [cf] + [vp] * 5 + [i64, i64, ci, vp]
-        L.tf_dropout_inplace_f32.restype = ci
-        L.tf_dropout_inplace_f32.argtypes = [vp, vp, cf, i64, vp]
-        L.tf_relu_dropout_bwd_f32.restype = ci
-        L.tf_relu_dropout_bwd_f32.argtypes = [vp, vp, cf, vp, i64, vp]
-        L.tf_add_layernorm_bwd_workspace_bytes.restype = i64
-        L.tf_add_layernorm_bwd_workspace_bytes.argtypes = [i64, ci]
-        L._dropout_bound = True
-    return L
+    return emu_lib.lib()   # bound from the headers (trackformer_amd._cabi.bind)
 
 
 def _al(a):

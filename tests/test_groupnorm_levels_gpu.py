@@ -31,10 +31,8 @@ def dev():
 
 @pytest.fixture(scope="module")
 def backend(dev):
-    import ctypes
     from trackformer_amd import _cabi
-    # a handle of its own on the loaded library: GL.bind() sets the argument types for ITS table structure
-    return GL.device_backend(ctypes.CDLL(_cabi.LIB_PATH), dev)
+    return GL.device_backend(_cabi.lib(), dev)
 
 
 def _check_level(got, lv, G, what):

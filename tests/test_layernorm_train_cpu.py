@@ -19,17 +19,7 @@ GUARD = 3            # canary rows behind dz, stats and the workspace
 
 
 def _lib():
-    L = emu_lib.lib()
-    if not getattr(L, "_layernorm_bwd_bound", False):
-        vp, ci, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
-        L.tf_add_layernorm_train_f32.restype = ci
-        L.tf_add_layernorm_train_f32.argtypes = [vp, vp, vp, vp, vp, vp, i64, ci, ctypes.c_float, vp]
-        L.tf_add_layernorm_bwd_workspace_bytes.restype = i64
-        L.tf_add_layernorm_bwd_workspace_bytes.argtypes = [i64, ci]
-        L.tf_add_layernorm_bwd_f32.restype = ci
-        L.tf_add_layernorm_bwd_f32.argtypes = [vp] * 9 + [i64, i64, ci, vp]
-        L._layernorm_bwd_bound = True
-    return L
+    return emu_lib.lib()   # bound from the headers (trackformer_amd._cabi.bind)
 
 
 def _al(a):

@@ -27,21 +27,7 @@ OUT_FLOOR_DGRAD = 2 * 2.0 ** -149
 
 
 def _lib():
-    L = emu_lib.lib()
-    if not getattr(L, "_linear_bwd_bound", False):
-        vp, ci, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
-        L.tf_linear_grad_stats_workspace_bytes.restype = i64
-        L.tf_linear_grad_stats_workspace_bytes.argtypes = [i64, ci, ci, ci]
-        L.tf_linear_grad_stats_f32.restype = ci
-        L.tf_linear_grad_stats_f32.argtypes = [vp, vp, vp, vp, i64, i64, ci, ci, ci, vp]
-        L.tf_linear_wgrad_workspace_bytes.restype = i64
-        L.tf_linear_wgrad_workspace_bytes.argtypes = [i64, ci, ci]
-        L.tf_linear_wgrad_split_f32.restype = ci
-        L.tf_linear_wgrad_split_f32.argtypes = [vp, vp, vp, vp, vp, vp, i64, i64, ci, ci, ci, vp]
-        L.tf_linear_dgrad_packed_f32.restype = ci
-        L.tf_linear_dgrad_packed_f32.argtypes = [vp, vp, vp, vp, i64, ci, ci, ci, vp]
-        L._linear_bwd_bound = True
-    return L
+    return emu_lib.lib()   # bound from the headers (trackformer_amd._cabi.bind)
 
 
 def _al(a):

@@ -1,8 +1,6 @@
 """CPU: the fused mask losses (include/tf_fused.h: THE MASK LOSSES; trackformer_amd/csrc/mask_loss.h) on the emulated library -- the
 kernels' own source under the SIMT emulator -- against float64 with the yardstick of tests/util_mask_losses.py, the yardstick's own
 self-tests, and the host logic of the route that needs no GPU."""
-import ctypes
-
 import numpy as np
 import pytest
 import torch
@@ -21,17 +19,7 @@ EMU_SHAPES = [s for s in M.SHAPES if s[2] * s[3] <= 128 * 160]
 
 
 def _lib():
-    L = emu_lib.lib()
-    if not getattr(L, "_mask_loss_bound", False):
-        vp, ci, i64, cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
-        L.tf_mask_loss_workspace_bytes.restype = i64
-        L.tf_mask_loss_workspace_bytes.argtypes = [ci, ci, ci]
-        L.tf_mask_loss_fwd_f32.restype = ci
-        L.tf_mask_loss_fwd_f32.argtypes = [vp] * 7 + [i64] + [ci] * 7 + [cf, cf, cf, vp]
-        L.tf_mask_loss_bwd_f32.restype = ci
-        L.tf_mask_loss_bwd_f32.argtypes = [vp] * 7 + [ci] * 7 + [cf, cf, cf, vp]
-        L._mask_loss_bound = True
-    return L
+    return emu_lib.lib()   # bound from the headers (trackformer_amd._cabi.bind)
 
 
 def _al(a, dt=np.float32):

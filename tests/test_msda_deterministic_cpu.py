@@ -37,22 +37,9 @@ CASES = [   # id, dtype, dict(N, M, D, Lq, P, shapes, encoder)
 ]
 
 
-# ---- binding of the new symbols on a ctypes library --------------------------------------------------------------------------------------
-def _bind(L):
-    vp, ci = ctypes.c_void_p, ctypes.c_int
-    L.tf_msda_backward_det_workspace_bytes.restype = ctypes.c_int64
-    L.tf_msda_backward_det_workspace_bytes.argtypes = [ci] * 8
-    for suf in ("f32", "f64"):
-        for tail in ("", "_dshapes"):
-            f = getattr(L, "tf_msda_backward_det_%s%s" % (suf, tail))
-            f.restype = ci
-            f.argtypes = [vp] * 9 + [ctypes.c_int64] + [ci] * 7 + [vp]
-    return L
-
-
 @pytest.fixture(scope="module")
 def emu():
-    return _bind(emu_lib.lib())
+    return emu_lib.lib()
 
 
 def _filled(shape, dtype, fill):

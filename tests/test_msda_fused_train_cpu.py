@@ -16,7 +16,7 @@ CANARY = -1234.5
 
 @pytest.fixture(scope="module")
 def lib():
-    return T.set_argtypes(emu_lib.lib())
+    return emu_lib.lib()
 
 
 def _grads(shape_loc, seed):

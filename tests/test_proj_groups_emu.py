@@ -4,12 +4,11 @@ x + x2) compute -- every kernel instantiation that is built (fp16 pieces with 32
 "groups_ti": without it these row counts would only reach the 32-row kernel; six terms with the 32-row blocks it has), rows below one
 tile / one tile + 1 / two tiles + a tail of the 96-row tile, full and narrow column chunks, with and without bias, dynamic LDS
 poisoned (the emulator's default), guard rows behind row M untouched."""
-import ctypes
-
 import numpy as np
 import pytest
 
 from tests import emu_lib
+from trackformer_amd import _cabi
 
 pytestmark = pytest.mark.skipif(not emu_lib.available(), reason="needs a host clang++ (ROCm's llvm) to build the emulated library")
 
@@ -25,18 +24,7 @@ GROUP_LISTS = {
 }
 
 
-class ProjGroup(ctypes.Structure):   # tf_proj_group of include/tf_fused.h
-    _fields_ = [("w_packed", ctypes.c_void_p), ("bias", ctypes.c_void_p), ("y", ctypes.c_void_p), ("N", ctypes.c_int),
-                ("add_x2", ctypes.c_int)]
-
-
-def _entry():
-    L = emu_lib.lib()
-    fn = L.tf_linear_groups_f32
-    fn.restype = ctypes.c_int
-    fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ProjGroup), ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
-                   ctypes.c_void_p]
-    return fn
+ProjGroup = _cabi.ProjGroup
 
 
 def linear_groups(x, x2, groups, guard_rows=GUARD):
@@ -51,7 +39,7 @@ def linear_groups(x, x2, groups, guard_rows=GUARD):
         keep += [pk, b]
         ys.append(y)
         d.w_packed, d.bias, d.y, d.N, d.add_x2 = pk.ctypes.data, emu_lib._p(b), y.ctypes.data, w.shape[0], int(add)
-    rc = _entry()(emu_lib._p(x), emu_lib._p(x2), descs, len(groups), M, x.shape[1], emu_lib.TERMS, None)
+    rc = emu_lib.lib().tf_linear_groups_f32(emu_lib._p(x), emu_lib._p(x2), descs, len(groups), M, x.shape[1], emu_lib.TERMS, None)
     return rc, ys
 
 
@@ -175,7 +163,7 @@ def test_groups_width_that_is_no_multiple_of_128():
 
 def test_groups_invalid_arguments_launch_nothing():
     x, x2, ws, bs = _data(33)
-    fn = _entry()
+    fn = emu_lib.lib().tf_linear_groups_f32
     xa, x2a = emu_lib._aligned(x), emu_lib._aligned(x2)
     pk = emu_lib._packed(ws[0])
     y = emu_lib._aligned(np.full((33, 256), np.nan, np.float32))

@@ -2,16 +2,15 @@
 tf_groupnorm_levels_nhwc_f32 -- GroupNorm of several pyramid levels in two launches into one token buffer (csrc/fused_ops.hip) -- and
 tf_conv_packed_partials_f32, the convolution entry that leaves its split-K partial sums for it.
 
-  * the ctypes binding of the two entries on ANY library handle (the emulated one does not go through trackformer_amd/_cabi.py)
   * restate(): the kernels' arithmetic operation by operation in numpy -- the order of every sum is part of the contract (no atomics:
     two calls give the same bits), so the comparison is BITWISE
   * run_levels(): one call with guard rows before, between and behind the levels' rows of the output, an image stride that is not
     HW * C, and a guarded workspace, on either backend
 
 A backend is a pair (lib, up, down): `up(numpy array) -> (keep-alive object, address)`, `down(object) -> numpy array`."""
-import ctypes
-
 import numpy as np
+
+from trackformer_amd import _cabi
 
 GUARD_ROWS = 2
 SENTINEL = np.float32(-7.25e11)       # what guard rows and unwritten output rows hold
@@ -19,20 +18,7 @@ WS_SENTINEL = -3.5e101
 ROWS_PER_BLOCK = 64                   # kGnRowsPerBlock
 
 
-class GnLevel(ctypes.Structure):      # tf_gn_level of include/tf_fused.h
-    _fields_ = [("src", ctypes.c_void_p), ("bias", ctypes.c_void_p), ("gamma", ctypes.c_void_p), ("beta", ctypes.c_void_p),
-                ("pieces", ctypes.c_int), ("HW", ctypes.c_int), ("row0", ctypes.c_int64)]
-
-
-def bind(L):
-    vp, ci, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
-    L.tf_groupnorm_levels_workspace_doubles.restype = i64
-    L.tf_groupnorm_levels_workspace_doubles.argtypes = [ctypes.POINTER(GnLevel), ci, ci, ci, ci]
-    L.tf_groupnorm_levels_nhwc_f32.restype = ci
-    L.tf_groupnorm_levels_nhwc_f32.argtypes = [ctypes.POINTER(GnLevel), ci, ci, ci, ci, ctypes.c_float, vp, i64, vp, vp]
-    L.tf_conv_packed_partials_f32.restype = ci
-    L.tf_conv_packed_partials_f32.argtypes = [vp, vp, vp, vp] + [ci] * 9 + [ctypes.POINTER(ci), vp]
-    return L
+GnLevel = _cabi.GnLevel
 
 
 # ---- the arithmetic, restated ------------------------------------------------------------------------------------------------------
@@ -132,7 +118,7 @@ def host_backend(L):
         out = buf[off:off + a.nbytes].view(a.dtype).reshape(a.shape)
         out[...] = a
         return out, out.ctypes.data
-    return bind(L), up, lambda o: o
+    return L, up, lambda o: o
 
 
 def device_backend(L, device="cuda"):
@@ -145,7 +131,7 @@ def device_backend(L, device="cuda"):
     def down(t):
         torch.cuda.synchronize()
         return t.cpu().numpy()
-    return bind(L), up, down
+    return L, up, down
 
 
 def run_levels(backend, levels, N, C, G, eps=1e-5, stream=None, order=None):

@@ -71,15 +71,6 @@ def make(cid, profile):
     return (value, shapes, refp, qproj, grad_out), (kw["M"], len(kw["shapes"]), kw["P"])
 
 
-def set_argtypes(lib):
-    vp, ci = ctypes.c_void_p, ctypes.c_int
-    lib.tf_msda_fused_prologue_f32.restype = ci
-    lib.tf_msda_fused_prologue_f32.argtypes = [vp, ci, vp, ci, ci, ci, vp, vp, vp] + [ci] * 5 + [vp]
-    lib.tf_msda_fused_backward_epilogue_f32.restype = ci
-    lib.tf_msda_fused_backward_epilogue_f32.argtypes = [vp, ci, vp, ci, ci, ci, vp, vp, vp, vp, vp, ci, ci, ci, vp] + [ci] * 5 + [vp]
-    return lib
-
-
 def _p(t):
     return None if t is None else t.data_ptr()
 

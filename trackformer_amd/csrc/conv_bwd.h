@@ -115,7 +115,7 @@ extern "C" int tf_conv3x3_wgrad_split_f32(const float *dy, const float *x, const
     else
         hipLaunchKernelGGL(conv3x3_wgrad_kernel<16>, grid, dim3(256), 0, s, dy, x, dy_scale2, x_scale2, out, (int)d.M, N, K, ktiles, p.spc, hin, win,
                            cin, d.hout, d.wout, stride);
-    if (hipGetLastError() != hipSuccess) return TF_MSDA_ERR_LAUNCH;
+    if (int rc = tfm::launched()) return rc;
     return p.msplit > 1 ? launch_splitk_reduce(out, nullptr, nullptr, dw, (long long)N * K, K, p.msplit, 0, s) : TF_MSDA_OK;
 }
 

@@ -296,7 +296,7 @@ extern "C" int tf_set_criterion_fwd_f32(const float *logits, const float *boxes,
     hipLaunchKernelGGL(set_criterion_fwd_kernel, dim3((unsigned)L), dim3(256), 0, static_cast<hipStream_t>(stream), logits, boxes, tgt_of,
                        reinterpret_cast<const long long *>(labels), tboxes, tgt_len, losses, card, class_error, B, Q, C, T, alpha, gamma,
                        num_boxes);
-    if (hipGetLastError() != hipSuccess) return TF_MSDA_ERR_LAUNCH;
+    if (int rc = tfm::launched()) return rc;
     tfm::note_kernel("set_criterion_fwd_f32");
     return TF_MSDA_OK;
 }
@@ -314,7 +314,7 @@ extern "C" int tf_set_criterion_bwd_f32(const float *G, const float *logits, con
     hipLaunchKernelGGL(set_criterion_bwd_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), G,
                        logits, boxes, tgt_of, reinterpret_cast<const long long *>(labels), tboxes, grad_logits, grad_boxes, rows, B * Q, C,
                        T, alpha, gamma, num_boxes);
-    if (hipGetLastError() != hipSuccess) return TF_MSDA_ERR_LAUNCH;
+    if (int rc = tfm::launched()) return rc;
     tfm::note_kernel("set_criterion_bwd_f32");
     return TF_MSDA_OK;
 }
@@ -329,7 +329,7 @@ extern "C" int tf_match_cost_f32(const float *logits, const float *boxes, const 
     const long long total = (long long)R * T;
     hipLaunchKernelGGL(match_cost_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), logits, boxes,
                        reinterpret_cast<const long long *>(tgt_ids), tgt_bbox, cost, total, C, T, w_class, w_bbox, w_giou, alpha, gamma);
-    if (hipGetLastError() != hipSuccess) return TF_MSDA_ERR_LAUNCH;
+    if (int rc = tfm::launched()) return rc;
     tfm::note_kernel("match_cost_f32");
     return TF_MSDA_OK;
 }

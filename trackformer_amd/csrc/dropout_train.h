@@ -121,7 +121,7 @@ extern "C" int tf_dropout_keep_u8(const int64_t *rng, float p, int64_t first, in
     hipLaunchKernelGGL(dropout_keep_u8_kernel, dim3((unsigned)stream_blocks(ngroups)), dim3(256), 0, static_cast<hipStream_t>(stream),
                        reinterpret_cast<const long long *>(rng), tfd::dropout_threshold(p), (long long)(first / 4), ngroups,
                        reinterpret_cast<unsigned *>(keep));
-    if (hipGetLastError() != hipSuccess) return TF_MSDA_ERR_LAUNCH;
+    if (int rc = tfm::launched()) return rc;
     tfm::note_kernel("dropout_keep_u8");
     return TF_MSDA_OK;
 }
@@ -132,7 +132,7 @@ extern "C" int tf_dropout_inplace_f32(float *y, const int64_t *rng, float p, int
     if (!tfd::dropout_p_ok(p) || n <= 0 || (n & 3) || !aligned16(y) || !word_aligned8(rng)) return TF_MSDA_ERR_BAD_DIMS;
     hipLaunchKernelGGL(dropout_inplace_kernel, dim3((unsigned)stream_blocks(n / 4)), dim3(256), 0, static_cast<hipStream_t>(stream), y,
                        reinterpret_cast<const long long *>(rng), tfd::dropout_threshold(p), tfd::dropout_scale(p), (long long)(n / 4));
-    if (hipGetLastError() != hipSuccess) return TF_MSDA_ERR_LAUNCH;
+    if (int rc = tfm::launched()) return rc;
     tfm::note_kernel("dropout_inplace_f32");
     return TF_MSDA_OK;
 }
@@ -143,7 +143,7 @@ extern "C" int tf_relu_dropout_bwd_f32(const float *dy, const float *y, float p,
     if (!tfd::dropout_p_ok(p) || n <= 0 || (n & 3) || !aligned16(dy) || !aligned16(y) || !aligned16(out)) return TF_MSDA_ERR_BAD_DIMS;
     hipLaunchKernelGGL(relu_dropout_bwd_kernel, dim3((unsigned)stream_blocks(n / 4)), dim3(256), 0, static_cast<hipStream_t>(stream), dy, y,
                        tfd::dropout_scale(p), out, (long long)(n / 4));
-    if (hipGetLastError() != hipSuccess) return TF_MSDA_ERR_LAUNCH;
+    if (int rc = tfm::launched()) return rc;
     tfm::note_kernel("relu_dropout_bwd_f32");
     return TF_MSDA_OK;
 }
@@ -162,7 +162,7 @@ extern "C" int tf_add_dropout_layernorm_train_f32(const float *x, const float *r
         hipLaunchKernelGGL(add_dropout_layernorm_kernel<decltype(maxch)::value>, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), x, res,
                            gamma, beta, reinterpret_cast<const long long *>(rng), T, scale, out, stats, (long long)rows, C, eps);
     });
-    if (hipGetLastError() != hipSuccess) return TF_MSDA_ERR_LAUNCH;
+    if (int rc = tfm::launched()) return rc;
     tfm::note_kernel("add_dropout_layernorm_stats_f32");
     return TF_MSDA_OK;
 }

@@ -47,6 +47,7 @@
 #include <type_traits>
 
 #include "host_dispatch.h"
+#include "launch_status.h"
 #include "msda_common.h"
 #include "split_product.h"
 #include "tf_fused.h"
@@ -399,11 +400,11 @@ int launch_ffn(const float *x, const u32x4 *w1, const float *b1, const u32x4 *w2
     constexpr size_t lds = ffn_lds_bytes<D>(TI, Split<SP>::NA);
     static_assert(lds <= 160 * 1024, "the two tiles do not fit the LDS of a CU");
     const void *fn = ln ? (const void *)&ffn_fused_kernel<SP, D, TI, true> : (const void *)&ffn_fused_kernel<SP, D, TI, false>;
-    if (lds > 64 * 1024 && !tfm::raise_dynamic_lds_limit(fn)) return TF_MSDA_ERR_LAUNCH;
+    if (lds > 64 * 1024 && !tfm::raise_dynamic_lds_limit(fn)) return tfm::record_hip(hipErrorInvalidValue);
     const int blocks = (M + 32 * TI - 1) / (32 * TI);
     void *argv[] = {(void *)&x, (void *)&w1, (void *)&b1, (void *)&w2, (void *)&b2, (void *)&res,
                     (void *)&gamma, (void *)&beta, (void *)&eps, (void *)&y, (void *)&M, (void *)&F};
-    return hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(Geo<D>::NT), argv, lds, s) == hipSuccess ? TF_MSDA_OK : TF_MSDA_ERR_LAUNCH;
+    return tfm::record_hip(hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(Geo<D>::NT), argv, lds, s));
 }
 
 // ---- tf_linear_res_ln_f32: y = [LayerNorm](residual + x . w^T + bias) for a D x D weight -- the attention's output
@@ -500,10 +501,10 @@ int launch_linln(const float *x, const u32x4 *w, const float *b, const float *re
     constexpr size_t lds = linln_lds_bytes<D>(TI, Split<SP>::NA);
     static_assert(lds <= 160 * 1024, "the activation tile does not fit the LDS of a CU");
     const void *fn = ln ? (const void *)&linear_res_ln_kernel<SP, D, TI, true> : (const void *)&linear_res_ln_kernel<SP, D, TI, false>;
-    if (lds > 64 * 1024 && !tfm::raise_dynamic_lds_limit(fn)) return TF_MSDA_ERR_LAUNCH;
+    if (lds > 64 * 1024 && !tfm::raise_dynamic_lds_limit(fn)) return tfm::record_hip(hipErrorInvalidValue);
     const int blocks = (M + 32 * TI - 1) / (32 * TI);
     void *argv[] = {(void *)&x, (void *)&w, (void *)&b, (void *)&res, (void *)&gamma, (void *)&beta, (void *)&eps, (void *)&y, (void *)&M};
-    return hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(Geo<D>::NT), argv, lds, s) == hipSuccess ? TF_MSDA_OK : TF_MSDA_ERR_LAUNCH;
+    return tfm::record_hip(hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(Geo<D>::NT), argv, lds, s));
 }
 
 template <int SP, int D>
@@ -827,10 +828,10 @@ int launch_groups(const float *x, const float *x2, int M, const ProjGroups &pg, 
     static_assert(lds_max <= 160 * 1024, "the activation tile and the tables do not fit the LDS of a CU");
     const size_t lds = tile + 2 * 4 * (size_t)pg.ncols;
     const void *fn = (const void *)&linear_groups_kernel<SP, TI>;
-    if (lds_max > 64 * 1024 && !tfm::raise_dynamic_lds_limit(fn)) return TF_MSDA_ERR_LAUNCH;
+    if (lds_max > 64 * 1024 && !tfm::raise_dynamic_lds_limit(fn)) return tfm::record_hip(hipErrorInvalidValue);
     const int blocks = (M + 32 * TI - 1) / (32 * TI);
     void *argv[] = {(void *)&x, (void *)&x2, (void *)&M, (void *)&pg};
-    return hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(256), argv, lds, s) == hipSuccess ? TF_MSDA_OK : TF_MSDA_ERR_LAUNCH;
+    return tfm::record_hip(hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(256), argv, lds, s));
 }
 
 }  // namespace

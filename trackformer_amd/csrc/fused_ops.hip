@@ -11,6 +11,7 @@
 #include <type_traits>
 
 #include "dropout_rng.h"
+#include "launch_status.h"
 #include "msda_common.h"
 #include "tf_fused.h"
 #include "tf_msda.h"
@@ -725,7 +726,7 @@ int tf_bias_relu_maxpool_f32(const float *x, const float *bias, float *out, int 
     if (total >= (1LL << 31)) return TF_MSDA_ERR_BAD_DIMS;
     hipLaunchKernelGGL(bias_relu_maxpool_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), x, bias,
                        out, H, W, C / 4, Ho, Wo, total);
-    return hipGetLastError() == hipSuccess ? TF_MSDA_OK : TF_MSDA_ERR_LAUNCH;
+    return tfm::launched();
 }
 
 int tf_box_refine_f32(const float *delta, const float *ref, float *out, int64_t rows, int ref_dim, float eps, void *stream)
@@ -736,7 +737,7 @@ int tf_box_refine_f32(const float *delta, const float *ref, float *out, int64_t 
     if (blocks > 0x7fffffffLL) return TF_MSDA_ERR_BAD_DIMS;
     hipLaunchKernelGGL(box_refine_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), delta, ref,
                        out, (long long)rows, ref_dim, eps);
-    return hipGetLastError() == hipSuccess ? TF_MSDA_OK : TF_MSDA_ERR_LAUNCH;
+    return tfm::launched();
 }
 
 int tf_postprocess_pack_f32(const float *logits, const float *boxes, float *out, int64_t Q, int C, float img_h, float img_w,
@@ -748,7 +749,7 @@ int tf_postprocess_pack_f32(const float *logits, const float *boxes, float *out,
     const long long blocks = (Q + 255) / 256;
     hipLaunchKernelGGL(postprocess_pack_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), logits, boxes,
                        out, (long long)Q, C, img_h, img_w, clip);
-    return hipGetLastError() == hipSuccess ? TF_MSDA_OK : TF_MSDA_ERR_LAUNCH;
+    return tfm::launched();
 }
 
 int tf_upsample_add_nhwc_f32(const float *low, const float *fpn, float *out, int N, int q_per_image, int h, int w, int H, int W, int C,
@@ -763,7 +764,7 @@ int tf_upsample_add_nhwc_f32(const float *low, const float *fpn, float *out, int
     if (blocks > 256 * 32) blocks = 256 * 32;
     hipLaunchKernelGGL(upsample_add_nhwc_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), low, fpn, out,
                        q_per_image, h, w, H, W, C / 4, (float)h / (float)H, (float)w / (float)W, total);
-    return hipGetLastError() == hipSuccess ? TF_MSDA_OK : TF_MSDA_ERR_LAUNCH;
+    return tfm::launched();
 }
 
 int tf_groupnorm_relu_conv3x3_c1_nhwc_f32(const float *x, const float *gamma, const float *beta, const float *weight, float bias,
@@ -777,7 +778,7 @@ int tf_groupnorm_relu_conv3x3_c1_nhwc_f32(const float *x, const float *gamma, co
     const int HW = H * W;
     const unsigned n_ws = 2u * (unsigned)N * (unsigned)G;
     hipLaunchKernelGGL(groupnorm_zero_kernel, dim3((n_ws + 255) / 256), dim3(256), 0, s, workspace, n_ws);   // (a kernel, not a memset node)
-    if (hipGetLastError() != hipSuccess) return TF_MSDA_ERR_LAUNCH;
+    if (int rc = tfm::launched()) return rc;
     const unsigned sblocks = (unsigned)((HW + kGnRowsPerBlock - 1) / kGnRowsPerBlock);
     hipLaunchKernelGGL(groupnorm_stats_kernel, dim3(sblocks, (unsigned)N), dim3(256), 0, s, x, workspace, HW, C, G, (long long)HW * C);
     const dim3 grid((unsigned)((W + 31) / 32), (unsigned)((H + 7) / 8), (unsigned)N);
@@ -787,7 +788,7 @@ int tf_groupnorm_relu_conv3x3_c1_nhwc_f32(const float *x, const float *gamma, co
     else
         hipLaunchKernelGGL(gn_relu_conv3x3_c1_kernel<32>, grid, dim3(256), 0, s, x, (const double *)workspace, gamma, beta, weight, bias,
                            out, H, W, G, eps);
-    return hipGetLastError() == hipSuccess ? TF_MSDA_OK : TF_MSDA_ERR_LAUNCH;
+    return tfm::launched();
 }
 
 int tf_mask_label_map_f32(const float *logits, const int *order, int16_t *label, int n_tracks, int h, int w, int pad_h, int pad_w, int img_h,
@@ -800,7 +801,7 @@ int tf_mask_label_map_f32(const float *logits, const int *order, int16_t *label,
     const dim3 grid((unsigned)((out_w + 31) / 32), (unsigned)((out_h + 7) / 8));
     hipLaunchKernelGGL(mask_label_map_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), logits, order, reinterpret_cast<short *>(label),
                        n_tracks, h, w, pad_h, pad_w, img_h, img_w, out_h, out_w, threshold);
-    return hipGetLastError() == hipSuccess ? TF_MSDA_OK : TF_MSDA_ERR_LAUNCH;
+    return tfm::launched();
 }
 
 static int groupnorm_nhwc_impl(const float *x, const float *gamma, const float *beta, float *out, double *workspace, int N, int HW,
@@ -822,7 +823,7 @@ static int groupnorm_nhwc_impl(const float *x, const float *gamma, const float *
     {
         const unsigned n_ws = 2u * (unsigned)N * (unsigned)G;
         hipLaunchKernelGGL(groupnorm_zero_kernel, dim3((n_ws + 255) / 256), dim3(256), 0, s, workspace, n_ws);
-        if (hipGetLastError() != hipSuccess) return TF_MSDA_ERR_LAUNCH;
+        if (int rc = tfm::launched()) return rc;
     }
     const unsigned sblocks = (unsigned)((HW + kGnRowsPerBlock - 1) / kGnRowsPerBlock);
     hipLaunchKernelGGL(groupnorm_stats_kernel, dim3(sblocks, (unsigned)N), dim3(256), 0, s, x, workspace, HW, C, G,
@@ -837,7 +838,7 @@ static int groupnorm_nhwc_impl(const float *x, const float *gamma, const float *
         hipLaunchKernelGGL(groupnorm_apply_kernel<false>, dim3((unsigned)ablocks, (unsigned)N), dim3(256), 0, s, x,
                            (const double *)workspace, gamma, beta, out, HW, C, G, eps, (long long)x_image_stride,
                            (long long)out_image_stride);
-    return hipGetLastError() == hipSuccess ? TF_MSDA_OK : TF_MSDA_ERR_LAUNCH;
+    return tfm::launched();
 }
 
 int tf_groupnorm_stats_nhwc_f32(const float *x, double *workspace, int N, int HW, int C, int G, int64_t x_image_stride, void *stream)
@@ -849,10 +850,10 @@ int tf_groupnorm_stats_nhwc_f32(const float *x, double *workspace, int N, int HW
     hipStream_t s = static_cast<hipStream_t>(stream);
     const unsigned n_ws = 2u * (unsigned)N * (unsigned)G;
     hipLaunchKernelGGL(groupnorm_zero_kernel, dim3((n_ws + 255) / 256), dim3(256), 0, s, workspace, n_ws);   // (a kernel, not a memset node)
-    if (hipGetLastError() != hipSuccess) return TF_MSDA_ERR_LAUNCH;
+    if (int rc = tfm::launched()) return rc;
     const unsigned sblocks = (unsigned)((HW + kGnRowsPerBlock - 1) / kGnRowsPerBlock);
     hipLaunchKernelGGL(groupnorm_stats_kernel, dim3(sblocks, (unsigned)N), dim3(256), 0, s, x, workspace, HW, C, G, (long long)x_image_stride);
-    return hipGetLastError() == hipSuccess ? TF_MSDA_OK : TF_MSDA_ERR_LAUNCH;
+    return tfm::launched();
 }
 
 int tf_groupnorm_nhwc_f32(const float *x, const float *gamma, const float *beta, float *out, double *workspace, int N,
@@ -925,10 +926,10 @@ int tf_groupnorm_levels_nhwc_f32(const tf_gn_level *levels, int nlevels, int N, 
     hipStream_t s = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(groupnorm_levels_stats_kernel, dim3((unsigned)sb, (unsigned)N), dim3(256), 0, s, lv, out, workspace, N, C, G,
                        (long long)out_image_stride, (int)sb);
-    if (hipGetLastError() != hipSuccess) return TF_MSDA_ERR_LAUNCH;
+    if (int rc = tfm::launched()) return rc;
     hipLaunchKernelGGL(groupnorm_levels_apply_kernel, dim3((unsigned)ab, (unsigned)N), dim3(256), 0, s, lv, out, (const double *)workspace, N,
                        C, G, eps, (long long)out_image_stride, (int)sb);
-    return hipGetLastError() == hipSuccess ? TF_MSDA_OK : TF_MSDA_ERR_LAUNCH;
+    return tfm::launched();
 }
 
 int tf_bias_act_f32(float *x, const float *bias, const float *residual, int64_t n, int C, int relu,
@@ -950,7 +951,7 @@ int tf_bias_act_f32(float *x, const float *bias, const float *residual, int64_t 
         hipLaunchKernelGGL((bias_act_kernel<false, true>), dim3((unsigned)blocks), dim3(256), 0, s, x, bias, residual, n4, C / 4);
     else
         hipLaunchKernelGGL((bias_act_kernel<false, false>), dim3((unsigned)blocks), dim3(256), 0, s, x, bias, residual, n4, C / 4);
-    return hipGetLastError() == hipSuccess ? TF_MSDA_OK : TF_MSDA_ERR_LAUNCH;
+    return tfm::launched();
 }
 
 static int add_layernorm_impl(const float *x, const float *res, const float *gamma, const float *beta, float *out, float *stats,
@@ -966,7 +967,7 @@ static int add_layernorm_impl(const float *x, const float *res, const float *gam
         hipLaunchKernelGGL((stats ? add_layernorm_kernel<MAXCH, true> : add_layernorm_kernel<MAXCH, false>), dim3(blocks), dim3(256), 0,
                            static_cast<hipStream_t>(stream), x, res, gamma, beta, out, stats, (long long)rows, C, eps);
     });
-    return hipGetLastError() == hipSuccess ? TF_MSDA_OK : TF_MSDA_ERR_LAUNCH;
+    return tfm::launched();
 }
 
 int tf_add_layernorm_f32(const float *x, const float *res, const float *gamma, const float *beta,

@@ -198,12 +198,12 @@ int add_layernorm_bwd_impl(const char *name, bool own_null, bool own_bad, const 
         hipLaunchKernelGGL((partials ? add_layernorm_bwd_kernel<MAXCH, true, DROP> : add_layernorm_bwd_kernel<MAXCH, false, DROP>), dim3((unsigned)nb),
                            dim3(256), 0, s, dy, x, res, gamma, stats, dz, partial, (long long)rows, C, ln_bwd_rows_per(rows), drop);
     });
-    if (hipGetLastError() != hipSuccess) return TF_MSDA_ERR_LAUNCH;
+    if (int rc = tfm::launched()) return rc;
     tfm::note_kernel(name);
     if (partials) {
         const dim3 grid((unsigned)((C / 4 + kLnRedQuads - 1) / kLnRedQuads), 2u);
         hipLaunchKernelGGL(add_layernorm_bwd_reduce_kernel, grid, dim3(256), 0, s, (const float *)partial, dgamma, dbeta, C, nb);
-        if (hipGetLastError() != hipSuccess) return TF_MSDA_ERR_LAUNCH;
+        if (int rc = tfm::launched()) return rc;
         tfm::note_kernel("add_layernorm_bwd_reduce_f32");
     }
     return TF_MSDA_OK;

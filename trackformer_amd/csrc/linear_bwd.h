@@ -369,11 +369,11 @@ extern "C" int tf_linear_grad_stats_f32(const float *a, float *scale2, float *co
     unsigned *pcmax = role == kStatsRole_Weight ? reinterpret_cast<unsigned *>(w) : nullptr;
     hipStream_t s = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(grad_stats_partial_kernel, dim3((unsigned)nb), dim3(256), 0, s, a, pmax, psum, pcmax, (long long)M, C, stats_rows_per(M));
-    if (hipGetLastError() != hipSuccess) return TF_MSDA_ERR_LAUNCH;
+    if (int rc = tfm::launched()) return rc;
     const int cblocks = (colsum || pcmax) ? ((C >> 2) + 255) / 256 : 0;
     hipLaunchKernelGGL(grad_stats_final_kernel, dim3((unsigned)(cblocks + 1)), dim3(256), 0, s, (const unsigned *)pmax, (const float *)psum,
                        (const unsigned *)pcmax, scale2, colsum, C, nb, role, sp == 16 ? 1 : 0);
-    return hipGetLastError() == hipSuccess ? TF_MSDA_OK : TF_MSDA_ERR_LAUNCH;
+    return tfm::launched();
 }
 
 extern "C" int64_t tf_linear_wgrad_workspace_bytes(int64_t M, int K, int N)
@@ -404,7 +404,7 @@ extern "C" int tf_linear_wgrad_split_f32(const float *dy, const float *x, const 
         hipLaunchKernelGGL(wgrad_kernel<3>, grid, dim3(256), 0, s, dy, x, dy_scale2, x_scale2, out, (int)M, N, K, ktiles, p.spc);
     else
         hipLaunchKernelGGL(wgrad_kernel<16>, grid, dim3(256), 0, s, dy, x, dy_scale2, x_scale2, out, (int)M, N, K, ktiles, p.spc);
-    if (hipGetLastError() != hipSuccess) return TF_MSDA_ERR_LAUNCH;
+    if (int rc = tfm::launched()) return rc;
     return p.msplit > 1 ? launch_splitk_reduce(out, nullptr, nullptr, dw, (long long)N * K, K, p.msplit, 0, s) : TF_MSDA_OK;
 }
 

@@ -28,6 +28,7 @@
 #include <atomic>
 #include <type_traits>
 
+#include "launch_status.h"
 #include "msda_common.h"
 #include "split_product.h"
 #include "tf_fused.h"
@@ -646,7 +647,7 @@ int launch_gemm(const float *x, const Weight &w, const float *bias, const float 
     };
     if (fits_bufstore(M, N)) go(std::true_type{});
     else go(std::false_type{});
-    return hipGetLastError() == hipSuccess ? TF_MSDA_OK : TF_MSDA_ERR_LAUNCH;
+    return tfm::launched();
 }
 
 template <int SP, int BM, int BN, bool PREFETCH>
@@ -658,7 +659,7 @@ int launch_add(const float *x, const float *x2, const Weight &w, const float *bi
         hipLaunchKernelGGL((split_gemm_add_kernel<SP, BM, BN, PREFETCH, true>), grid, dim3(THREADS), 0, s, x, x2, w.p[0], w.p[1], w.p[2], w.scale, bias, y, M, K, N);
     else
         hipLaunchKernelGGL((split_gemm_add_kernel<SP, BM, BN, PREFETCH, false>), grid, dim3(THREADS), 0, s, x, x2, w.p[0], w.p[1], w.p[2], w.scale, bias, y, M, K, N);
-    return hipGetLastError() == hipSuccess ? TF_MSDA_OK : TF_MSDA_ERR_LAUNCH;
+    return tfm::launched();
 }
 
 // The weight arguments of the C ABI -> scheme (split_product.h): (w_hi, w_mid, w_lo) -> 3 (six bf16 terms), (w_hi, w_mid, NULL,
@@ -708,7 +709,7 @@ int linear_split_sp(const float *x, const Weight &w, const float *bias, const fl
             hipLaunchKernelGGL((split_gemm_deep_kernel<SP, true, SS>), grid, dim3(THREADS), 0, s, x, w.p[0], w.p[1], w.p[2], w.scale, bias, y, M, K, N);  \
         else                                                                                                                                      \
             hipLaunchKernelGGL((split_gemm_deep_kernel<SP, false, SS>), grid, dim3(THREADS), 0, s, x, w.p[0], w.p[1], w.p[2], w.scale, bias, y, M, K, N); \
-        return hipGetLastError() == hipSuccess ? TF_MSDA_OK : TF_MSDA_ERR_LAUNCH;                                                                 \
+        return tfm::launched();                                                                                                                   \
     }
             TF_DEEP(8) TF_DEEP(9) TF_DEEP(32) TF_DEEP(36)
 #undef TF_DEEP
@@ -746,7 +747,7 @@ int conv_launch_sp(const float *x, const Weight &w, const float *bias, float *ou
     } else {
         relu ? launch(split_conv3_kernel<SP, 64, 64, true>, 64) : launch(split_conv3_kernel<SP, 64, 64, false>, 64);
     }
-    return hipGetLastError() == hipSuccess ? TF_MSDA_OK : TF_MSDA_ERR_LAUNCH;
+    return tfm::launched();
 }
 
 int conv_split_impl(const float *x, const void *w_hi, const void *w_mid, const void *w_lo, const float *w_scale, const float *bias,
@@ -789,7 +790,7 @@ int conv_split_impl(const float *x, const void *w_hi, const void *w_mid, const v
         const long long mn4 = M * cout / 4;
         hipLaunchKernelGGL(conv_splitk_reduce_kernel, dim3((unsigned)((mn4 + 255) / 256)), dim3(256), 0, s, workspace, bias, y, mn4,
                            cout / 4, (int)gz, relu);
-        if (hipGetLastError() != hipSuccess) return TF_MSDA_ERR_LAUNCH;
+        if (int rc = tfm::launched()) return rc;
     }
     return TF_MSDA_OK;
 }

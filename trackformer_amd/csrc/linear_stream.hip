@@ -35,6 +35,7 @@
 #include <type_traits>
 
 #include "host_dispatch.h"
+#include "launch_status.h"
 #include "msda_common.h"
 #include "split_product.h"
 #include "tf_fused.h"
@@ -977,7 +978,7 @@ int launch_splitk_reduce(const float *partials, const float *bias, const float *
     const long long n4 = count / 4;
     hipLaunchKernelGGL(stream_splitk_reduce_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, partials, bias, res, out, n4, cols / 4,
                        pieces, relu);
-    return hipGetLastError() == hipSuccess ? TF_MSDA_OK : TF_MSDA_ERR_LAUNCH;
+    return tfm::launched();
 }
 
 template <int SP, int TI, int TJ, int WC, bool CONV, bool XSC = false>
@@ -999,7 +1000,7 @@ int launch_stream(const StreamCall &c, hipStream_t s)
     hipLaunchKernelGGL((stream_gemm_kernel<SP, TI, TJ, WC, CONV, XSC>), dim3((unsigned)gx, (unsigned)gz), dim3(kThreads), 0, s, c.x, c.wp,
                        (partial && !XSC) ? nullptr : c.bias, partial ? nullptr : c.res, out, c.M, c.K, c.N, mblocks, nblocks, partial ? 0 : c.relu,
                        kslices, c.cv);   // (XSC: `bias` is scale2 -- every partial sum is staged with s and leaves with 1 / s)
-    if (hipGetLastError() != hipSuccess) return TF_MSDA_ERR_LAUNCH;
+    if (int rc = tfm::launched()) return rc;
     if (c.deferred != nullptr) {
         *c.deferred = gz;
         return TF_MSDA_OK;
@@ -1065,7 +1066,7 @@ int launch_halo(const StreamCall &c, hipStream_t s, const HaloMerge mg = HaloMer
     hipLaunchKernelGGL((conv3x3_halo_kernel<SP, TI, TJ, WC, MRG, XSC>), dim3((unsigned)gx, (unsigned)gz), dim3(kThreads), 0, s, c.x, c.wp,
                        (partial && !XSC) ? nullptr : c.bias, partial ? nullptr : c.res, out, c.N, nblocks, (int)npatches, tiles_x, tiles_y,
                        partial ? 0 : c.relu, cslices, c.cv, mg);   // (XSC: as launch_stream)
-    if (hipGetLastError() != hipSuccess) return TF_MSDA_ERR_LAUNCH;
+    if (int rc = tfm::launched()) return rc;
     if (c.deferred != nullptr) {
         *c.deferred = gz;
         return TF_MSDA_OK;
@@ -1112,10 +1113,10 @@ int launch_dma(const StreamCall &c, hipStream_t s)
     const long long gx = (long long)((mblocks + 7) / 8) * 8 * nblocks;
     if (gx > 0x7fffffffLL) return TF_MSDA_ERR_BAD_DIMS;
     const void *fn = (const void *)&dma_gemm_kernel<SP, TI, TJ, STAGES>;
-    if (!tfm::raise_dynamic_lds_limit(fn)) return TF_MSDA_ERR_LAUNCH;
+    if (!tfm::raise_dynamic_lds_limit(fn)) return tfm::record_hip(hipErrorInvalidValue);
     hipLaunchKernelGGL((dma_gemm_kernel<SP, TI, TJ, STAGES>), dim3((unsigned)gx), dim3(kThreads), lds, s, c.x, c.wp, c.bias, c.res, c.y,
                        c.M, c.K, c.N, mblocks, nblocks, c.relu);
-    return hipGetLastError() == hipSuccess ? TF_MSDA_OK : TF_MSDA_ERR_LAUNCH;
+    return tfm::launched();
 }
 
 template <int SP>
@@ -1172,7 +1173,7 @@ extern "C" int tf_debug_stream_trace_buffer(void *device_buffer, int *blocks, in
     if (blocks) *blocks = kTraceBlocks;
     if (slices) *slices = kTraceSlices;
     if (points) *points = kTracePoints;
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_stream_trace), &p, sizeof(p)) == hipSuccess ? TF_MSDA_OK : TF_MSDA_ERR_LAUNCH;
+    return tfm::record_hip(hipMemcpyToSymbol(HIP_SYMBOL(g_stream_trace), &p, sizeof(p)));
 }
 #endif
 
@@ -1204,7 +1205,7 @@ extern "C" int tf_linear_pack_weight_f32(const float *w, void *packed, int K, in
         hipLaunchKernelGGL(pack_scale_kernel, dim3((unsigned)((npad + 3) / 4)), dim3(256), 0, s, w, rs, K, N, (int)npad);
         hipLaunchKernelGGL(pack_weight_kernel<16>, dim3((unsigned)blocks), dim3(256), 0, s, w, out, (const float *)rs, K, N, total);
     }
-    return hipGetLastError() == hipSuccess ? TF_MSDA_OK : TF_MSDA_ERR_LAUNCH;
+    return tfm::launched();
 }
 
 extern "C" int tf_linear_packed_f32(const float *x, const void *w_packed, const float *bias, const float *residual, float *y,

@@ -32,6 +32,7 @@
 #define TF_MASK_LOSS_H_
 
 #include "host_dispatch.h"
+#include "launch_status.h"
 
 namespace {
 
@@ -288,13 +289,13 @@ extern "C" int tf_mask_loss_fwd_f32(const float *src, const uint8_t *tgt, const 
         const tfm::KernelVariant kv = {(const void *)&mask_loss_fwd_kernel, "mask_loss_fwd_f32"};
         void *argv[] = {(void *)&src, (void *)&tgt, (void *)&pair_src, (void *)&pair_tgt, (void *)&partial, (void *)&tiles, (void *)&BQ,
                         (void *)&T,   (void *)&h,   (void *)&w,        (void *)&H,        (void *)&W,       (void *)&alpha, (void *)&gamma};
-        if (hipLaunchKernel(kv.fn, dim3((unsigned)n * (unsigned)tiles), dim3(kMaskChunk), argv, 0, s) != hipSuccess) return TF_MSDA_ERR_LAUNCH;
+        if (int rc = tfm::record_hip(hipLaunchKernel(kv.fn, dim3((unsigned)n * (unsigned)tiles), dim3(kMaskChunk), argv, 0, s))) return rc;
         tfm::note_kernel(kv.name);
     }
     const tfm::KernelVariant kv = {(const void *)&mask_loss_finish_kernel, "mask_loss_finish_f32"};
     const double *cpartial = partial;
     void *argv[] = {(void *)&cpartial, (void *)&sums, (void *)&losses, (void *)&n, (void *)&tiles, (void *)&H, (void *)&W, (void *)&num_boxes};
-    if (hipLaunchKernel(kv.fn, dim3(1), dim3(256), argv, 0, s) != hipSuccess) return TF_MSDA_ERR_LAUNCH;
+    if (int rc = tfm::record_hip(hipLaunchKernel(kv.fn, dim3(1), dim3(256), argv, 0, s))) return rc;
     tfm::note_kernel(kv.name);
     return TF_MSDA_OK;
 }
@@ -312,8 +313,8 @@ extern "C" int tf_mask_loss_bwd_f32(const float *G, const float *src, const uint
     void *argv[] = {(void *)&G, (void *)&src, (void *)&tgt, (void *)&pair_tgt, (void *)&row_pair, (void *)&sums, (void *)&grad_src,
                     (void *)&bpr, (void *)&n, (void *)&T,   (void *)&h,        (void *)&w,        (void *)&H,    (void *)&W,
                     (void *)&alpha, (void *)&gamma, (void *)&num_boxes};
-    if (hipLaunchKernel(kv.fn, dim3((unsigned)BQ * (unsigned)bpr), dim3(256), argv, 0, static_cast<hipStream_t>(stream)) != hipSuccess)
-        return TF_MSDA_ERR_LAUNCH;
+    if (int rc = tfm::record_hip(hipLaunchKernel(kv.fn, dim3((unsigned)BQ * (unsigned)bpr), dim3(256), argv, 0, static_cast<hipStream_t>(stream))))
+        return rc;
     tfm::note_kernel(kv.name);
     return TF_MSDA_OK;
 }

@@ -291,14 +291,14 @@ extern "C" int tf_mha_core_train_f32(const float *q, const float *k, const float
     const bool one = Lk <= per_batch;
     const void *fn = D == 32 ? (one ? (const void *)&mha_mfma_stream_kernel<32, 1, true> : (const void *)&mha_mfma_stream_kernel<32, 2, true>)
                              : (one ? (const void *)&mha_mfma_stream_kernel<36, 1, true> : (const void *)&mha_mfma_stream_kernel<36, 2, true>);
-    if (lds > 64 * 1024 && !tfm::raise_dynamic_lds_limit(fn)) return TF_MSDA_ERR_LAUNCH;
+    if (lds > 64 * 1024 && !tfm::raise_dynamic_lds_limit(fn)) return tfm::record_hip(hipErrorInvalidValue);
     const long long *rngp = reinterpret_cast<const long long *>(rng);
     unsigned T = rng ? tfd::dropout_threshold(p) : 0u;
     float sp = rng ? tfd::dropout_scale(p) : 1.f;
     const dim3 grid((unsigned)((Lq + TQ - 1) / TQ), (unsigned)H, (unsigned)N);
     void *args[] = {(void *)&q, (void *)&k, (void *)&v, (void *)&out, (void *)&key_mask, (void *)&Lq, (void *)&Lk, (void *)&ldq, (void *)&ldk,
                     (void *)&ldv, (void *)&ldo, (void *)&scale, (void *)&lkp, (void *)&stats, (void *)&rngp, (void *)&T, (void *)&sp};
-    return hipLaunchKernel(fn, grid, dim3(THREADS), args, lds, static_cast<hipStream_t>(stream)) == hipSuccess ? TF_MSDA_OK : TF_MSDA_ERR_LAUNCH;
+    return tfm::record_hip(hipLaunchKernel(fn, grid, dim3(THREADS), args, lds, static_cast<hipStream_t>(stream)));
 }
 
 extern "C" int tf_mha_core_bwd_f32(const float *dout, const float *q, const float *k, const float *v, const float *out, const float *stats,
@@ -329,7 +329,7 @@ extern "C" int tf_mha_core_bwd_f32(const float *dout, const float *q, const floa
     const size_t lds = (size_t)2 * (THREADS / 64) * TQ * D * sizeof(float);
     const dim3 grid((unsigned)((Lq + TQ - 1) / TQ + (Lk + TQ - 1) / TQ), (unsigned)H, (unsigned)N);
     void *args[] = {(void *)&a};
-    return hipLaunchKernel(fn, grid, dim3(THREADS), args, lds, static_cast<hipStream_t>(stream)) == hipSuccess ? TF_MSDA_OK : TF_MSDA_ERR_LAUNCH;
+    return tfm::record_hip(hipLaunchKernel(fn, grid, dim3(THREADS), args, lds, static_cast<hipStream_t>(stream)));
 }
 
 #endif /* TF_MHA_BWD_H_ */

@@ -29,6 +29,7 @@
 
 #include "dropout_rng.h"
 #include "host_dispatch.h"
+#include "launch_status.h"
 #include "msda_common.h"
 #include "tf_fused.h"
 #include "tf_msda.h"
@@ -587,7 +588,7 @@ extern "C" int tf_mha_core_f32(const float *q, const float *k, const float *v, f
             case 36: fns = one ? (const void *)&mha_mfma_stream_kernel<36, 1> : (const void *)&mha_mfma_stream_kernel<36, 2>; break;
             default: fns = one ? (const void *)&mha_mfma_stream_kernel<64, 1> : (const void *)&mha_mfma_stream_kernel<64, 2>; break;
             }
-            if (lds > 64 * 1024 && !tfm::raise_dynamic_lds_limit(fns)) return TF_MSDA_ERR_LAUNCH;
+            if (lds > 64 * 1024 && !tfm::raise_dynamic_lds_limit(fns)) return tfm::record_hip(hipErrorInvalidValue);
             const dim3 grids((unsigned)((Lq + TQ - 1) / TQ), (unsigned)H, (unsigned)N);
             float *no_stats = nullptr;
             const long long *no_rng = nullptr;
@@ -596,8 +597,7 @@ extern "C" int tf_mha_core_f32(const float *q, const float *k, const float *v, f
             void *args[] = {(void *)&q, (void *)&k, (void *)&v, (void *)&out, (void *)&key_mask, (void *)&Lq, (void *)&Lk, (void *)&ldq,
                             (void *)&ldk, (void *)&ldv, (void *)&ldo, (void *)&scale, (void *)&lkp, (void *)&no_stats, (void *)&no_rng,
                             (void *)&no_T, (void *)&no_scale};
-            return hipLaunchKernel(fns, grids, dim3(THREADS), args, lds, static_cast<hipStream_t>(stream)) == hipSuccess
-                       ? TF_MSDA_OK : TF_MSDA_ERR_LAUNCH;
+            return tfm::record_hip(hipLaunchKernel(fns, grids, dim3(THREADS), args, lds, static_cast<hipStream_t>(stream)));
         }
     }
     if (use_mfma && (D == 16 || D == 32 || D == 36 || D == 64)) {
@@ -619,12 +619,11 @@ extern "C" int tf_mha_core_f32(const float *q, const float *k, const float *v, f
             const size_t lds = (size_t)(two ? 2 : 1) * kc * dp * sizeof(float) + fixed;
             const void *fnm = D == 16 ? (const void *)&mha_mfma_kernel<16> : D == 32 ? (const void *)&mha_mfma_kernel<32>
                               : D == 36 ? (const void *)&mha_mfma_kernel<36> : (const void *)&mha_mfma_kernel<64>;
-            if (lds > 64 * 1024 && !tfm::raise_dynamic_lds_limit(fnm)) return TF_MSDA_ERR_LAUNCH;
+            if (lds > 64 * 1024 && !tfm::raise_dynamic_lds_limit(fnm)) return tfm::record_hip(hipErrorInvalidValue);
             const dim3 gridm((unsigned)((Lq + TQ - 1) / TQ), (unsigned)H, (unsigned)N);
             void *argm[] = {(void *)&q, (void *)&k, (void *)&v, (void *)&out, (void *)&key_mask, (void *)&Lq, (void *)&Lk, (void *)&ldq,
                             (void *)&ldk, (void *)&ldv, (void *)&ldo, (void *)&scale, (void *)&lkp, (void *)&kc, (void *)&two};
-            return hipLaunchKernel(fnm, gridm, dim3(THREADS), argm, lds, static_cast<hipStream_t>(stream)) == hipSuccess
-                       ? TF_MSDA_OK : TF_MSDA_ERR_LAUNCH;
+            return tfm::record_hip(hipLaunchKernel(fnm, gridm, dim3(THREADS), argm, lds, static_cast<hipStream_t>(stream)));
         }
     }
     const int lk_pad = (Lk + 1) & ~1;
@@ -646,12 +645,11 @@ extern "C" int tf_mha_core_f32(const float *q, const float *k, const float *v, f
     case 16: fn = (const void *)&mha_core_kernel<16>; break;
     default: return TF_MSDA_ERR_BAD_DIMS;   // head dimensions 16, 32, 36, 64
     }
-    if (lds > 64 * 1024 && !tfm::raise_dynamic_lds_limit(fn)) return TF_MSDA_ERR_LAUNCH;
+    if (lds > 64 * 1024 && !tfm::raise_dynamic_lds_limit(fn)) return tfm::record_hip(hipErrorInvalidValue);
     const dim3 grid((unsigned)((Lq + TQ - 1) / TQ), (unsigned)H, (unsigned)N);
     void *argv[] = {(void *)&q, (void *)&k, (void *)&v, (void *)&out, (void *)&key_mask, (void *)&Lq, (void *)&Lk, (void *)&ldq,
                     (void *)&ldk, (void *)&ldv, (void *)&ldo, (void *)&scale, (void *)&lk_pad, (void *)&kc};
-    return hipLaunchKernel(fn, grid, dim3(THREADS), argv, lds, static_cast<hipStream_t>(stream)) == hipSuccess
-               ? TF_MSDA_OK : TF_MSDA_ERR_LAUNCH;
+    return tfm::record_hip(hipLaunchKernel(fn, grid, dim3(THREADS), argv, lds, static_cast<hipStream_t>(stream)));
 }
 
 #include "mha_bwd.h"

@@ -1,6 +1,6 @@
 // trackformer_amd/csrc/msda_bwd_det.h -- msda_bwd_det<T>: the bitwise-reproducible MSDeformAttn backward
 // (tf_msda_backward_det_*, include/tf_msda.h).  Included from msda_hip.hip inside its anonymous namespace, behind
-// backward_impl: it uses that file's fill_level_table / build_level_table / record_hip and msda_point.h's Tap / make_tap.
+// backward_impl: it uses that file's fill_level_table / build_level_table, launch_status.h's record_hip and msda_point.h's Tap / make_tap.
 //
 // The default backward kernels scatter grad_value with float atomics, whose summation order is whatever the memory system
 // makes of it.  Here no float atomic appears anywhere: every contribution is stored once, the contributions of one

@@ -14,6 +14,7 @@
 #include <mutex>
 
 #include "host_dispatch.h"
+#include "launch_status.h"
 #include "msda_common.h"
 
 namespace tfm {

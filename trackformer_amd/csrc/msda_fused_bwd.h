@@ -2,7 +2,7 @@
 //   msda_fused_prologue<f32>      qproj, reference points -> loc [N, Lq, M, L, P, 2], attn [N, Lq, M, L, P]
 //   msda_fused_bwd_epilogue<f32>  grad_loc, grad_attn     -> the offset and logit columns of grad_qproj, grad_ref
 // (tf_msda_fused_prologue_f32 / tf_msda_fused_backward_epilogue_f32, include/tf_msda.h).  Included from msda_hip.hip inside its
-// anonymous namespace, behind backward_det_impl: it uses that file's record_hip / is_aligned / note_kernel.
+// anonymous namespace, behind backward_det_impl: it uses that file's is_aligned / note_kernel and launch_status.h's record_hip.
 //
 // Between the two runs the operator's own backward (tf_msda_backward_* or tf_msda_backward_det_*) on the prologue's loc / attn,
 // so autograd keeps value, the reference points and qproj only and the backward never walks an element-wise ATen chain.

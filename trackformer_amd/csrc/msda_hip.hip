@@ -73,7 +73,6 @@ struct alignas(sizeof(T) * VEC) Pack {
     T v[VEC];
 };
 
-thread_local int g_last_hip_error = 0;
 thread_local const char *g_last_kernel = "";
 
 // ---------------------------------------------------------------------------------------------
@@ -1407,15 +1406,6 @@ hipError_t launch(const void *fn, unsigned grid, size_t lds, hipStream_t stream,
     return hipLaunchKernel(fn, dim3(grid), dim3(kThreads), argv, lds, stream);
 }
 
-int record_hip(hipError_t e)
-{
-    if (e != hipSuccess) {
-        g_last_hip_error = (int)e;
-        return TF_MSDA_ERR_LAUNCH;
-    }
-    return TF_MSDA_OK;
-}
-
 int build_level_table(const int64_t *shapes_host, int L, int S, LevelTable *lt)
 {
     long long acc = 0;
@@ -2022,7 +2012,7 @@ const char *tf_msda_strerror(int status)
     }
 }
 
-int tf_msda_last_hip_error(void) { return g_last_hip_error; }
+int tf_msda_last_hip_error(void) { return tfm::g_last_hip_error; }
 
 int tf_msda_set_tiled(int mode)
 {

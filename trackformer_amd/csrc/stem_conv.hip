@@ -28,6 +28,7 @@
 
 #include <type_traits>
 
+#include "launch_status.h"
 #include "msda_common.h"
 #include "split_product.h"
 #include "tf_fused.h"
@@ -217,5 +218,5 @@ extern "C" int tf_stem_conv7x7_f32(const float *x, const void *w_packed, const f
     };
     if (sp == 3) go(std::integral_constant<int, 3>{});
     else go(std::integral_constant<int, 16>{});
-    return hipGetLastError() == hipSuccess ? TF_MSDA_OK : TF_MSDA_ERR_LAUNCH;
+    return tfm::launched();
 }
