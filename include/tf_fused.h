@@ -411,6 +411,55 @@ int tf_conv3x3_dgrad_packed_f32(const float *dy, const float *dy_scale2, const v
                                 int nimg, int h, int w, int cin, int cout, int terms, void *stream);
 
 /*
+ * THE BACKWARD OF THE STRIDE-2 CONVOLUTIONS  (trackformer_amd/csrc/conv_strided_bwd.h; reference: the autograd of the first bottleneck of
+ * ResNet-50's layer2-4 in models/backbone.py: its 3 x 3 conv2, padding 1, and the 1 x 1 projection of its identity branch, no padding).
+ * Tensors as in the section above: x / dx [nimg, h, w, cin], dy [nimg, ho, wo, cout], ho = (h - 1) / 2 + 1, wo = (w - 1) / 2 + 1.
+ *
+ *   tf_conv_dgrad_stride2_packed_f32   ks = 3: the weight is [cout, 3, 3, cin];  ks = 1: [cout, cin].
+ *       The input pixel (iy, ix) = (2 a + py, 2 b + px) belongs to the parity class c = 2 py + px, which has
+ *       ceil((h - py) / 2) x ceil((w - px) / 2) pixels per image and T_c = (1 + py)(1 + px) taps:
+ *           dx[n, 2 a + py, 2 b + px, ci] = sum over the class's taps (da, db) and co of  dy[n, a + da, b + db, co] w[co, ky, kx, ci]
+ *           py = 0: da = 0 with ky = 1;   py = 1: da = 0 with ky = 2, then da = 1 with ky = 0;   (db, kx) from px alike
+ *       -- a dy row a + 1 = ho or column b + 1 = wo is an exact zero that is never read (not the next row, not the next image).  ks = 1
+ *       is the class (0, 0) alone, dx[n, 2 a, 2 b] = dy[n, a, b] . w; the pixels of the other three classes are written as +0.
+ *       wcls_packed holds the class weights one behind the other, c = 0, 1, 2, 3 (ks = 1: c = 0 only): class c is
+ *       tf_linear_pack_weight_f32 of W_c [cin, T_c cout] with K = T_c cout, N = cin, where column (t cout + co) of W_c is
+ *       w[co, ky, kx, ci] for the t-th tap of the class in the order (da, db) = (0, 0), (0, 1), (1, 0), (1, 1) restricted to the class;
+ *       the image of class c starts tf_linear_packed_bytes(T_c' cout, cin, terms) bytes behind that of each class c' < c.
+ *       Each class is one launch of tf_conv_packed_f32's stream form (a stride-1 window of T_c taps over dy, no padding) in the
+ *       scaled-activation instantiation of tf_conv3x3_dgrad_packed_f32: dy is multiplied by s as it is staged, every partial sum leaves
+ *       its workgroup multiplied by 1 / s (dy_scale2 = {s, 1 / s}; NULL: the plain instantiation).  The contraction of the longest class
+ *       is cut into ksplit pieces (1 .. 64), that of the others in proportion (ceil(ksplit T_c / 4)), never below 64 products per
+ *       piece; the launches write compact class images into `workspace` (tf_conv_dgrad_stride2_workspace_bytes(...), 16-byte aligned,
+ *       needed for every ksplit), and ONE further launch writes every element of dx exactly once: the pieces of its class added in
+ *       the order 0, 1, ...  No zero-inserted copy of dy, no atomics; the order of every sum is a function of the arguments' shape.
+ *       Per class the result equals (1 / s) . tf_conv_packed_f32-style products of s dy: the bound of THE BACKWARD OF A LINEAR with
+ *       the contraction length T_c cout.
+ *       cout % 64 == 0, cin % 4 == 0, 16-byte aligned dy / wcls_packed / dx / workspace, dy and dx (+ 256 rows) below 3 GiB.
+ *   tf_conv1x1_strided_wgrad_split_f32   dw[co, ci] = sum_m dy[m, co] x[n, 2 ho, 2 wo, ci], m = (n, ho, wo), stride = 2 only (any other
+ *       value: TF_MSDA_ERR_BAD_DIMS -- the stride-1 1 x 1 is tf_linear_wgrad_split_f32 on the pixel matrix): the kernel of
+ *       tf_linear_wgrad_split_f32 with the row address of x replaced, as tf_conv3x3_wgrad_split_f32 but without taps or padding.
+ *       dy_scale2 from tf_linear_grad_stats_f32 of dy [M, cout] (role 0), x_scale2 = t[cin] | 1 / t[cin] of x viewed as
+ *       [nimg hin win, cin] (role 1: one scale per input channel over ALL pixels of x).  The chunks of the pixel loop, the
+ *       "wgrad_msplit" knob and the second launch are those of tf_linear_wgrad_split_f32 for (M, K = cin, N = cout);
+ *       tf_conv1x1_strided_wgrad_workspace_bytes(...) = msplit cout cin 4 bytes (0 for one chunk).  The result equals
+ *       tf_linear_wgrad_split_f32(dy, G, dy_scale2, x_scale2) on the gathered matrix G[M, cin] BIT FOR BIT; G is never built.
+ *       cin % 4 == 0, cout % 4 == 0, 16-byte aligned dy / x / dw / x_scale2 / workspace, dy / x / dw below 3 GiB each.
+ * Checked before any GPU work, in this order: NULL pointer (tf_conv_dgrad_stride2_packed_f32: dy / wcls_packed / dx / workspace;
+ * the weight gradient: all but the workspace) -> TF_MSDA_ERR_NULL_POINTER; dimensions, ks, ksplit outside 1 .. 64, unknown terms,
+ * alignment -> TF_MSDA_ERR_BAD_DIMS; workspace too small (the weight gradient: NULL or misaligned too) -> TF_MSDA_ERR_WORKSPACE.  The
+ * ..._workspace_bytes functions return -1 for dimensions their entry point rejects.
+ */
+int64_t tf_conv_dgrad_stride2_workspace_bytes(int nimg, int h, int w, int cin, int cout, int ks, int ksplit);
+int tf_conv_dgrad_stride2_packed_f32(const float *dy, const float *dy_scale2, const void *wcls_packed, float *dx, void *workspace,
+                                     int64_t workspace_bytes, int ksplit, int nimg, int h, int w, int cin, int cout, int ks, int terms,
+                                     void *stream);
+int64_t tf_conv1x1_strided_wgrad_workspace_bytes(int nimg, int hin, int win, int cin, int cout, int stride);
+int tf_conv1x1_strided_wgrad_split_f32(const float *dy, const float *x, const float *dy_scale2, const float *x_scale2, float *dw,
+                                       void *workspace, int64_t workspace_bytes, int nimg, int hin, int win, int cin, int cout, int stride,
+                                       int terms, void *stream);
+
+/*
  * THE BACKWARD OF THE RESIDUAL LAYERNORM  out = LayerNorm(x + res) gamma + beta  (trackformer_amd/csrc/layernorm_bwd.h; reference: the
  * autograd of `src = src + dropout(src2); src = norm(src)` of models/deformable_transformer.py, fp32).  With z = x + res (z = x for
  * res == NULL), mean / rstd = 1 / sqrt(var + eps) of the row, xh = (z - mean) rstd and g = gamma dy:

@@ -230,9 +230,12 @@ def set_train_fold(on: bool) -> bool:
 # OPT-IN (TF_SPLIT_CONV_TRAIN=1 / set_split_conv_training(True)): the convolutions of the TRAINABLE bottlenecks (mode 2 above: layer2-4)
 # through fused.conv_train -- the inference route's forward kernels and the library's own input- and weight-gradient kernels
 # (include/tf_fused.h: THE BACKWARD OF A 3 x 3 CONVOLUTION; the 1 x 1 stride-1 layers through fused.linear_train's) instead of
-# F.conv2d's MIOpen / CK forward and backward; the weight fold and _BiasAct stay what they are.  NOT covered: the strided 1 x 1
-# projections of the identity branch, the input gradient of the three stride-2 3 x 3 layers (torch inside the backward, counted), the
-# stem, input_proj.  OFF by default: whether it is faster inside a training step is a measurement (tools/bench_conv_backward.py,
+# F.conv2d's MIOpen / CK forward and backward; the weight fold and _BiasAct stay what they are.  The six STRIDE-2 layers -- the strided
+# 1 x 1 projections of the identity branch and the input gradient of the three stride-2 3 x 3 layers -- join the route under a second
+# switch, fused.set_strided_conv_training(True) / TF_STRIDED_CONV_TRAIN=1 (include/tf_fused.h: THE BACKWARD OF THE STRIDE-2
+# CONVOLUTIONS); without it the projections stay F.conv2d and those three input gradients are torch's inside the backward, counted.
+# With both switches on every convolution of layer2-4 has an own, atomic-free backward.  NOT covered: the stem, input_proj, the mask
+# head, GroupNorm.  OFF by default: whether it is faster inside a training step is a measurement (tools/bench_conv_backward.py,
 # profiles/conv_backward_bench.json), not a promise.
 _split_conv_train = None    # None: follow TF_SPLIT_CONV_TRAIN (unset: off)
 
@@ -261,6 +264,8 @@ def _conv_train(x, conv, w_f):
         return fused.conv_train(x, w_f.permute(0, 2, 3, 1).reshape(cout, 9 * cin), conv.stride[0])
     if conv.kernel_size == (1, 1) and conv.padding == (0, 0) and conv.stride == (1, 1):
         return fused.conv_train(x, w_f.reshape(cout, cin), 1)
+    if (conv.kernel_size == (1, 1) and conv.padding == (0, 0) and conv.stride == (2, 2) and fused.strided_conv_training_enabled()):
+        return fused.conv_train(x, w_f.reshape(cout, cin), 2)   # the projection of a stage's first identity branch
     return None
 
 

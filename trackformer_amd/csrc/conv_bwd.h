@@ -63,40 +63,42 @@ conv3x3_wgrad_kernel(const float *__restrict__ dy, const float *__restrict__ x, 
     wgrad_tile<SP>(dy, dy_scale2, out, M, N, K, ktiles, spc, WgradRowsConv3{x, x_scale2, hin, win, cin, hout, wout, stride, 0, 0, 0, false});
 }
 
-// the dimensions of the weight gradient's GEMM, or false for what the entry point rejects
+// the dimensions of the weight gradient's GEMM, or false for what the entry point rejects; taps: 9 (3 x 3, padding 1) or 1 (1 x 1, no
+// padding: conv_strided_bwd.h), strides min_stride .. 2
 struct ConvWgradDims {
     long long M;
     int hout, wout, K;
 };
-inline bool conv3x3_wgrad_dims(int nimg, int hin, int win, int cin, int cout, int stride, ConvWgradDims &d)
+inline bool conv_wgrad_dims(int taps, int min_stride, int nimg, int hin, int win, int cin, int cout, int stride, ConvWgradDims &d)
 {
-    if (nimg <= 0 || hin <= 0 || win <= 0 || cin <= 0 || cout <= 0 || (cin & 3) || (cout & 3) || (stride != 1 && stride != 2)) return false;
+    if (nimg <= 0 || hin <= 0 || win <= 0 || cin <= 0 || cout <= 0 || (cin & 3) || (cout & 3) || stride < min_stride || stride > 2) return false;
     d.hout = (hin - 1) / stride + 1;
     d.wout = (win - 1) / stride + 1;
     d.M = (long long)nimg * d.hout * d.wout;
-    if (d.M > 0x7fffffffLL || 9LL * cin > 0x7fffffffLL) return false;
-    d.K = 9 * cin;
+    if (d.M > 0x7fffffffLL || (long long)taps * cin > 0x7fffffffLL) return false;
+    d.K = taps * cin;
     return true;
 }
 
-}  // namespace
-
-extern "C" int64_t tf_conv3x3_wgrad_workspace_bytes(int nimg, int hin, int win, int cin, int cout, int stride)
+inline int64_t conv_wgrad_workspace_bytes(int taps, int min_stride, int nimg, int hin, int win, int cin, int cout, int stride)
 {
     ConvWgradDims d;
-    if (!conv3x3_wgrad_dims(nimg, hin, win, cin, cout, stride, d)) return -1;
+    if (!conv_wgrad_dims(taps, min_stride, nimg, hin, win, cin, cout, stride, d)) return -1;
     const WgradPlan p = wgrad_plan(d.M, d.K, cout);
     return p.msplit > 1 ? (int64_t)p.msplit * cout * d.K * 4 : 0;
 }
 
-extern "C" int tf_conv3x3_wgrad_split_f32(const float *dy, const float *x, const float *dy_scale2, const float *x_scale2, float *dw,
-                                          void *workspace, int64_t workspace_bytes, int nimg, int hin, int win, int cin, int cout, int stride,
-                                          int terms, void *stream)
+// the gates, the chunks of the pixel loop and the second pass of a convolution's weight gradient (ONE copy for the 3 x 3 and the strided
+// 1 x 1); launch(sp, grid, stream, out, M, N, K, ktiles, spc, dims) starts the kernel with the layer's row map
+template <class LAUNCH>
+int conv_wgrad_entry(int taps, int min_stride, const float *dy, const float *x, const float *dy_scale2, const float *x_scale2, float *dw,
+                     void *workspace, int64_t workspace_bytes, int nimg, int hin, int win, int cin, int cout, int stride, int terms, void *stream,
+                     LAUNCH launch)
 {
     if (!dy || !x || !dy_scale2 || !x_scale2 || !dw) return TF_MSDA_ERR_NULL_POINTER;
     const int sp = split_scheme(terms);
     ConvWgradDims d;
-    if (!conv3x3_wgrad_dims(nimg, hin, win, cin, cout, stride, d) || sp == 0) return TF_MSDA_ERR_BAD_DIMS;
+    if (!conv_wgrad_dims(taps, min_stride, nimg, hin, win, cin, cout, stride, d) || sp == 0) return TF_MSDA_ERR_BAD_DIMS;
     const int N = cout, K = d.K;
     if (d.M * N * 4 >= 0xC0000000LL || (long long)nimg * hin * win * cin * 4 >= 0xC0000000LL || (long long)N * K * 4 >= 0xC0000000LL)
         return TF_MSDA_ERR_BAD_DIMS;
@@ -108,15 +110,31 @@ extern "C" int tf_conv3x3_wgrad_split_f32(const float *dy, const float *x, const
     if ((long long)ntiles * ktiles > 0x7fffffffLL) return TF_MSDA_ERR_BAD_DIMS;
     hipStream_t s = static_cast<hipStream_t>(stream);
     float *out = p.msplit > 1 ? static_cast<float *>(workspace) : dw;
-    const dim3 grid((unsigned)(ntiles * ktiles), (unsigned)p.msplit);
-    if (sp == 3)
-        hipLaunchKernelGGL(conv3x3_wgrad_kernel<3>, grid, dim3(256), 0, s, dy, x, dy_scale2, x_scale2, out, (int)d.M, N, K, ktiles, p.spc, hin, win,
-                           cin, d.hout, d.wout, stride);
-    else
-        hipLaunchKernelGGL(conv3x3_wgrad_kernel<16>, grid, dim3(256), 0, s, dy, x, dy_scale2, x_scale2, out, (int)d.M, N, K, ktiles, p.spc, hin, win,
-                           cin, d.hout, d.wout, stride);
+    launch(sp, dim3((unsigned)(ntiles * ktiles), (unsigned)p.msplit), s, out, (int)d.M, N, K, ktiles, p.spc, d);
     if (int rc = tfm::launched()) return rc;
     return p.msplit > 1 ? launch_splitk_reduce(out, nullptr, nullptr, dw, (long long)N * K, K, p.msplit, 0, s) : TF_MSDA_OK;
+}
+
+}  // namespace
+
+extern "C" int64_t tf_conv3x3_wgrad_workspace_bytes(int nimg, int hin, int win, int cin, int cout, int stride)
+{
+    return conv_wgrad_workspace_bytes(9, 1, nimg, hin, win, cin, cout, stride);
+}
+
+extern "C" int tf_conv3x3_wgrad_split_f32(const float *dy, const float *x, const float *dy_scale2, const float *x_scale2, float *dw,
+                                          void *workspace, int64_t workspace_bytes, int nimg, int hin, int win, int cin, int cout, int stride,
+                                          int terms, void *stream)
+{
+    return conv_wgrad_entry(9, 1, dy, x, dy_scale2, x_scale2, dw, workspace, workspace_bytes, nimg, hin, win, cin, cout, stride, terms, stream,
+                            [=](int sp, dim3 grid, hipStream_t s, float *out, int M, int N, int K, int ktiles, int spc, const ConvWgradDims &d) {
+                                if (sp == 3)
+                                    hipLaunchKernelGGL(conv3x3_wgrad_kernel<3>, grid, dim3(256), 0, s, dy, x, dy_scale2, x_scale2, out, M, N, K, ktiles, spc,
+                                                       hin, win, cin, d.hout, d.wout, stride);
+                                else
+                                    hipLaunchKernelGGL(conv3x3_wgrad_kernel<16>, grid, dim3(256), 0, s, dy, x, dy_scale2, x_scale2, out, M, N, K, ktiles, spc,
+                                                       hin, win, cin, d.hout, d.wout, stride);
+                            });
 }
 
 // dx = conv3x3(dy, w_rot): tf_conv_packed_f32(ks = 3, stride = 1, the same workspace / ksplit) with dy [nimg, h, w, cout] as the input

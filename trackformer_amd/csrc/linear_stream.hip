@@ -1273,3 +1273,5 @@ extern "C" int tf_conv_packed_partials_f32(const float *x, const void *w_packed,
 #include "linear_bwd.h"
 // the backward of a 3 x 3 convolution: the same two products through the convolution's index map
 #include "conv_bwd.h"
+// the backward of the stride-2 convolutions: the input gradient by parity classes, the weight gradient of the strided 1 x 1
+#include "conv_strided_bwd.h"

@@ -1652,7 +1652,10 @@ class _NotApplicable(Exception):
 def _packed_image(t, attr, rows, cols, terms, source):
     """Fragment-order image (tf_linear_pack_weight_f32) of the contiguous [rows, cols] tensor source() derives from t, cached on t as
     `attr` under its source_key(), per `terms`; None when it cannot be built (shape; stream capture without a cached image).  The
-    images of the training path only: no publish barrier, the stream that built an image is remembered instead."""
+    images of the training path only: no publish barrier, the stream that built an image is remembered instead.
+    rows and cols may be LISTS (source() then returns as many tensors): the images one behind the other in one buffer."""
+    many = isinstance(rows, (list, tuple))
+    shapes = list(zip(rows, cols)) if many else [(rows, cols)]
     cache = getattr(t, attr, None)
     key = source_key(t)
     if cache is None or cache[0] != key:
@@ -1663,14 +1666,17 @@ def _packed_image(t, attr, rows, cols, terms, source):
     if hit is None:
         if capturing:
             return None   # never build a cached buffer inside a graph's memory pool
-        nbytes = _cabi.lib().tf_linear_packed_bytes(rows, cols, terms)
-        if nbytes <= 0:
+        sizes = [_cabi.lib().tf_linear_packed_bytes(r, c, terms) for r, c in shapes]
+        if min(sizes) <= 0:
             return None
         with torch.cuda.device(t.device):
-            src = source()
-            buf = torch.empty(nbytes, dtype=torch.uint8, device=t.device)
-            rc = _cabi.lib().tf_linear_pack_weight_f32(src.data_ptr(), buf.data_ptr(), rows, cols, terms, _stream(t.device))
-        _cabi.check(rc, "tf_linear_pack_weight_f32")
+            srcs = source() if many else [source()]
+            buf = torch.empty(sum(sizes), dtype=torch.uint8, device=t.device)
+            at = buf.data_ptr()
+            for src, (r, c), nbytes in zip(srcs, shapes, sizes):
+                rc = _cabi.lib().tf_linear_pack_weight_f32(src.data_ptr(), at, r, c, terms, _stream(t.device))
+                _cabi.check(rc, "tf_linear_pack_weight_f32")
+                at += nbytes
         hit = (buf, torch.cuda.current_stream(t.device))
         cache[1][terms] = hit
     elif not capturing and hit[1] != torch.cuda.current_stream(t.device):
@@ -2269,16 +2275,93 @@ def attention_reference(x, value_in, mha, key_padding_mask, p, rng):
 # The switch lives with its caller (backbone.set_split_conv_training / TF_SPLIT_CONV_TRAIN=1: the trainable bottlenecks' conv + FrozenBN
 # pairs); conv_train below is the operator.  3 x 3, padding 1, stride 1 or 2: the forward is conv3x3() (bit-identical to the inference
 # route), the backward the library's statistics, input-gradient (stride 1) and weight-gradient kernels.  1 x 1, stride 1: _LinearTrain on
-# the pixel matrix of the channels_last activation.  No float atomics: bit-identical from call to call.  NOT covered: the strided 1 x 1
-# projections, the input gradient of a stride-2 3 x 3 (torch, counted), the stem, input_proj, the mask head, GroupNorm.
+# the pixel matrix of the channels_last activation.  No float atomics: bit-identical from call to call.
+# The STRIDE-2 layers (set_strided_conv_training below / TF_STRIDED_CONV_TRAIN=1, a switch of its own, off by default; include/tf_fused.h:
+# THE BACKWARD OF THE STRIDE-2 CONVOLUTIONS; csrc/conv_strided_bwd.h): the input gradient of a stride-2 3 x 3 by parity classes
+# (tf_conv_dgrad_stride2_packed_f32), and the strided 1 x 1 projection -- forward conv3x3(), input gradient the same entry point with
+# ks = 1, weight gradient tf_conv1x1_strided_wgrad_split_f32.  With that switch off the strided 1 x 1 is not conv_train's and the input
+# gradient of a stride-2 3 x 3 is torch's (counted).  NOT covered: the stem, input_proj, the mask head, GroupNorm.
 _conv_train_counts = {"fwd_own": 0, "fwd_torch": 0, "dgrad_own": 0, "dgrad_torch": 0, "wgrad_own": 0, "wgrad_torch": 0}
+_strided_conv_train = None    # None: follow TF_STRIDED_CONV_TRAIN (unset: off)
 
 
 def conv_train_counts(reset=False):
     """How conv_train's calls went: forwards it ran (fwd_own) or declined on device tensors (fwd_torch: the caller's F.conv2d), and
-    the input / weight gradients of its 3 x 3 calls by the library's own kernels or by torch.  (The gradients of the 1 x 1 calls are
-    linear_train's: train_route_counts().)"""
+    the input / weight gradients of its 3 x 3 and strided 1 x 1 calls by the library's own kernels or by torch.  (The gradients of
+    the stride-1 1 x 1 calls are linear_train's: train_route_counts().)"""
     return _read_counts(_conv_train_counts, reset)
+
+
+def strided_conv_training_enabled():
+    if _strided_conv_train is not None:
+        return _strided_conv_train
+    return os.environ.get("TF_STRIDED_CONV_TRAIN", "0") not in ("", "0")
+
+
+def set_strided_conv_training(flag):
+    """Switch conv_train's own backward of the stride-2 convolutions on or off (process-wide; None: follow TF_STRIDED_CONV_TRAIN again);
+    returns the previous setting."""
+    global _strided_conv_train
+    prev = strided_conv_training_enabled()
+    _strided_conv_train = None if flag is None else bool(flag)
+    return _switched(prev, strided_conv_training_enabled())
+
+
+def _packed_weight_classes(w, terms, ks):
+    """Fragment-order images of the four parity-class weights W_c [Cin, T_c Cout] of a tap-major 3 x 3 weight [Cout, 9 Cin] -- or of the
+    one class w^T of a 1 x 1 weight [Cout, Cin] -- one behind the other in one buffer (the `wcls_packed` of
+    tf_conv_dgrad_stride2_packed_f32), cached on w under its source_key() with the rules of _packed_weight_rot; None when it cannot
+    be built (shape; stream capture without a cached image)."""
+    cout = w.shape[0]
+    if ks == 1:
+        cin = w.shape[1]
+        return _packed_image(w, "_tf_packed_cls", [cout], [cin], terms, lambda: [w.detach().t().contiguous()])
+    cin = w.shape[1] // 9
+    taps = ((1,), (2, 0))   # by parity: the tap rows (columns) in the order of the dy rows (columns) a, a + 1 they read
+
+    def classes():
+        w4 = w.detach().view(cout, 3, 3, cin)
+        return [torch.stack([w4[:, ky, kx] for ky in taps[py] for kx in taps[px]]).permute(2, 0, 1).reshape(cin, -1).contiguous()
+                for py in (0, 1) for px in (0, 1)]
+    return _packed_image(w, "_tf_packed_cls", [t * cout for t in (1, 2, 2, 4)], [cin] * 4, terms, classes)
+
+
+def _strided_dgrad_gates(n, h, w, cin, cout):
+    """The shapes tf_conv_dgrad_stride2_packed_f32 takes (its own checks, made here so that the fallback is chosen before any work)."""
+    ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+    return cout % 64 == 0 and cin % 4 == 0 and (n * h * w + 256) * cin * 4 < 0xC0000000 and n * ho * wo * cout * 4 < 0xC0000000
+
+
+# _conv_ksplit's policy tuple for the stride-2 input gradient, PINNED to the values the forward's policy has today (pieces of at least
+# 256 products): set_conv_ksplit_policy / TF_CONV_KSPLIT_POLICY tune the inference route and do not move this cut.  Measured on an
+# MI355X in the cfg-3 small step, tests/test_conv_strided_backward_step_gpu.py: with this tuple backbone layer3's worst element stands
+# at 3.8 / 3.4-3.8 of the harness's 4 yardsticks (the switches alone / every training switch on); pieces of 128 products from 256 products
+# on, (768, 300, 4, 8), were tried and are WORSE there: 4.2, outside the bound.
+_STRIDED_DGRAD_KSPLIT_POLICY = (768, 300, 8, 32)
+
+
+def _strided_dgrad_ksplit(n, h, w, cin, cout, ks):
+    """Pieces the longest contraction of the stride-2 input gradient (4 Cout products of the odd-odd class; Cout for a 1 x 1) is cut
+    into: _conv_ksplit on that class's (pixels, products, Cin) -- a function of the shape alone.  The shorter classes are cut in
+    proportion inside the library."""
+    if ks == 1:
+        return _conv_ksplit(n * ((h + 1) // 2) * ((w + 1) // 2), cout, cin, _STRIDED_DGRAD_KSPLIT_POLICY)
+    return _conv_ksplit(max(1, n * (h // 2) * (w // 2)), 4 * cout, cin, _STRIDED_DGRAD_KSPLIT_POLICY)
+
+
+def _strided_dgrad(dyn, s_dy, packed, n, h, w, cin, cout, ks, terms, stream):
+    """tf_conv_dgrad_stride2_packed_f32 -> dx [n, h, w, cin] (NHWC)."""
+    L = _cabi.lib()
+    ksplit = _strided_dgrad_ksplit(n, h, w, cin, cout, ks)
+    nbytes = int(L.tf_conv_dgrad_stride2_workspace_bytes(n, h, w, cin, cout, ks, ksplit))
+    if nbytes < 0:
+        _cabi.check(-2, "tf_conv_dgrad_stride2_packed_f32")
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dyn.device)
+    dxn = torch.empty((n, h, w, cin), dtype=torch.float32, device=dyn.device)
+    rc = L.tf_conv_dgrad_stride2_packed_f32(dyn.data_ptr(), s_dy.data_ptr(), packed.data_ptr(), dxn.data_ptr(), ws.data_ptr(), nbytes, ksplit,
+                                            n, h, w, cin, cout, ks, terms, stream)
+    _cabi.check(rc, "tf_conv_dgrad_stride2_packed_f32")
+    return dxn
 
 
 def _packed_weight_rot(w_taps, terms):
@@ -2333,6 +2416,71 @@ class _Conv1x1Train(torch.autograd.Function):
         return (None if dx2 is None else dx2.view(n, h, wd, cin).permute(0, 3, 1, 2)), dw, None
 
 
+def _conv_backward(needs, dy, x, w2, ks, stride, terms):
+    """(dx, dw) of conv_train's convolutions -- ks = 3: padding 1, stride 1 or 2, w2 [Cout, 9 Cin] tap-major; ks = 1: the stride-2
+    projection without padding, w2 [Cout, Cin] --: the statistics of dy, the input gradient (stride 1: tf_conv3x3_dgrad_packed_f32;
+    stride 2: tf_conv_dgrad_stride2_packed_f32 under set_strided_conv_training), the statistics of x (one scale per input channel over
+    ALL pixels of x) and the weight gradient (tf_conv3x3_wgrad_split_f32 / tf_conv1x1_strided_wgrad_split_f32); a gradient whose
+    kernel does not take the call is torch.ops.aten.convolution_backward on the same tensors.  Counted in _conv_train_counts."""
+    need_x, need_w = needs[0], needs[1]
+    n, cin, h, w = x.shape
+    cout, taps = w2.shape[0], ks * ks
+    ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
+    M = n * ho * wo
+    L = _cabi.lib()
+    dyn = _aligned(dy.permute(0, 2, 3, 1))   # NHWC: the storage of a channels_last gradient
+    xn = x.permute(0, 2, 3, 1)     # (contiguous: conv3x3 took x)
+    if xn.data_ptr() % 16:
+        xn = xn.clone(memory_format=torch.contiguous_format)
+    fp32 = dy.dtype == torch.float32
+    own_w = fp32 and cin % 4 == 0 and cout % 4 == 0 and max(M * cout, n * h * w * cin, cout * taps * cin) * 4 < 0xC0000000
+    own_x = (fp32 and ks == 3 and stride == 1 and cout % 64 == 0 and cin % 4 == 0 and (M + 256) * cin * 4 < 0xC0000000
+             and M * cout * 4 < 0xC0000000)
+    own_x2 = fp32 and stride == 2 and (ks == 1 or strided_conv_training_enabled()) and _strided_dgrad_gates(n, h, w, cin, cout)
+    dx = dw = None
+    with torch.cuda.device(dy.device), one_stream():
+        stream = _stream(dy.device)
+        packed_rot = _packed_weight_rot(w2, terms) if need_x and own_x else None
+        packed_cls = _packed_weight_classes(w2, terms, ks) if need_x and own_x2 else None
+        do_x, do_w = packed_rot is not None or packed_cls is not None, need_w and own_w
+        s_dy = _grad_stats(dyn.view(M, cout), 0, terms, False)[0] if (do_x or do_w) else None
+        if packed_cls is not None:   # stride 2: stride-1 windows over dy, one per parity class of the input pixel
+            dx = _strided_dgrad(dyn, s_dy, packed_cls, n, h, w, cin, cout, ks, terms, stream).permute(0, 3, 1, 2)
+        elif do_x:
+            # the contraction is cut as the forward's is (few pixels under a long K: more workgroups, and no accumulator walks
+            # all 9 Cout products)
+            ksplit = _conv_ksplit(M, 9 * cout, cin, _HALO_KSPLIT_POLICY if _conv_halo else None)
+            dxn = torch.empty((n, h, w, cin), dtype=torch.float32, device=dy.device)
+            wsx = torch.empty((ksplit, M * cin), dtype=torch.float32, device=dy.device) if ksplit > 1 else None
+            rc = L.tf_conv3x3_dgrad_packed_f32(dyn.data_ptr(), s_dy.data_ptr(), packed_rot.data_ptr(), dxn.data_ptr(), _ptr(wsx), ksplit,
+                                               n, h, w, cin, cout, terms, stream)
+            _cabi.check(rc, "tf_conv3x3_dgrad_packed_f32")
+            dx = dxn.permute(0, 3, 1, 2)
+        if do_w:
+            s_x, _ = _grad_stats(xn.view(n * h * w, cin), 1, terms, False)
+            name = "tf_conv3x3_wgrad" if ks == 3 else "tf_conv1x1_strided_wgrad"
+            nbytes = int(getattr(L, name + "_workspace_bytes")(n, h, w, cin, cout, stride))
+            ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dy.device)
+            dw = torch.empty((cout, taps * cin), dtype=torch.float32, device=dy.device)
+            rc = getattr(L, name + "_split_f32")(dyn.data_ptr(), xn.data_ptr(), s_dy.data_ptr(), s_x.data_ptr(), dw.data_ptr(), ws.data_ptr(),
+                                                 nbytes, n, h, w, cin, cout, stride, terms, stream)
+            _cabi.check(rc, name + "_split_f32")
+        mask = [need_x and not do_x, need_w and not do_w, False]
+        if mask[0] or mask[1]:   # what the kernels do not take: torch, on the same tensors
+            w4 = w2.detach().view(cout, ks, ks, cin).permute(0, 3, 1, 2)   # OIHW shape over its channels_last storage
+            pad = ks // 2
+            tx, tw, _ = torch.ops.aten.convolution_backward(dy, x, w4, None, [stride, stride], [pad, pad], [1, 1], False, [0, 0], 1, mask)
+            if mask[0]:
+                dx = tx
+            if mask[1]:
+                dw = tw.permute(0, 2, 3, 1).reshape(cout, taps * cin)
+    if need_x:
+        _conv_train_counts["dgrad_own" if do_x else "dgrad_torch"] += 1
+    if need_w:
+        _conv_train_counts["wgrad_own" if do_w else "wgrad_torch"] += 1
+    return dx, dw
+
+
 class _Conv3x3Train(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w_taps, stride, terms):
@@ -2348,58 +2496,30 @@ class _Conv3x3Train(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, dy):
         x, w_taps = ctx.saved_tensors
-        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        stride, terms = ctx.stride, ctx.terms
-        n, cin, h, w = x.shape
-        cout = w_taps.shape[0]
-        ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
-        M = n * ho * wo
-        L = _cabi.lib()
-        dyn = _aligned(dy.permute(0, 2, 3, 1))   # NHWC: the storage of a channels_last gradient
-        xn = x.permute(0, 2, 3, 1)     # (contiguous: conv3x3 took x)
-        if xn.data_ptr() % 16:
-            xn = xn.clone(memory_format=torch.contiguous_format)
-        fp32 = dy.dtype == torch.float32
-        own_w = fp32 and cin % 4 == 0 and cout % 4 == 0 and max(M * cout, n * h * w * cin, cout * 9 * cin) * 4 < 0xC0000000
-        own_x = (fp32 and stride == 1 and cout % 64 == 0 and cin % 4 == 0 and (M + 256) * cin * 4 < 0xC0000000
-                 and M * cout * 4 < 0xC0000000)
-        dx = dw = None
-        with torch.cuda.device(dy.device), one_stream():
-            stream = _stream(dy.device)
-            packed_rot = _packed_weight_rot(w_taps, terms) if need_x and own_x else None
-            do_x, do_w = packed_rot is not None, need_w and own_w
-            s_dy = _grad_stats(dyn.view(M, cout), 0, terms, False)[0] if (do_x or do_w) else None
-            if do_x:
-                # the contraction is cut as the forward's is (few pixels under a long K: more workgroups, and no accumulator walks
-                # all 9 Cout products)
-                ksplit = _conv_ksplit(M, 9 * cout, cin, _HALO_KSPLIT_POLICY if _conv_halo else None)
-                dxn = torch.empty((n, h, w, cin), dtype=torch.float32, device=dy.device)
-                wsx = torch.empty((ksplit, M * cin), dtype=torch.float32, device=dy.device) if ksplit > 1 else None
-                rc = L.tf_conv3x3_dgrad_packed_f32(dyn.data_ptr(), s_dy.data_ptr(), packed_rot.data_ptr(), dxn.data_ptr(), _ptr(wsx), ksplit,
-                                                   n, h, w, cin, cout, terms, stream)
-                _cabi.check(rc, "tf_conv3x3_dgrad_packed_f32")
-                dx = dxn.permute(0, 3, 1, 2)
-            if do_w:
-                s_x, _ = _grad_stats(xn.view(n * h * w, cin), 1, terms, False)
-                nbytes = int(L.tf_conv3x3_wgrad_workspace_bytes(n, h, w, cin, cout, stride))
-                ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dy.device)
-                dw = torch.empty((cout, 9 * cin), dtype=torch.float32, device=dy.device)
-                rc = L.tf_conv3x3_wgrad_split_f32(dyn.data_ptr(), xn.data_ptr(), s_dy.data_ptr(), s_x.data_ptr(), dw.data_ptr(), ws.data_ptr(),
-                                                  nbytes, n, h, w, cin, cout, stride, terms, stream)
-                _cabi.check(rc, "tf_conv3x3_wgrad_split_f32")
-            mask = [need_x and not do_x, need_w and not do_w, False]
-            if mask[0] or mask[1]:   # what the kernels do not take: torch, on the same tensors
-                w4 = w_taps.detach().view(cout, 3, 3, cin).permute(0, 3, 1, 2)   # OIHW shape over its channels_last storage
-                tx, tw, _ = torch.ops.aten.convolution_backward(dy, x, w4, None, [stride, stride], [1, 1], [1, 1], False, [0, 0], 1, mask)
-                if mask[0]:
-                    dx = tx
-                if mask[1]:
-                    dw = tw.permute(0, 2, 3, 1).reshape(cout, 9 * cin)
-        if need_x:
-            _conv_train_counts["dgrad_own" if do_x else "dgrad_torch"] += 1
-        if need_w:
-            _conv_train_counts["wgrad_own" if do_w else "wgrad_torch"] += 1
-        return dx, dw, None, None
+        return _conv_backward(ctx.needs_input_grad, dy, x, w_taps, 3, ctx.stride, ctx.terms) + (None, None)
+
+
+class _Conv1x1StridedTrain(torch.autograd.Function):
+    """The stride-2 1 x 1 projection of a bottleneck's identity branch (no padding): forward conv3x3() with the [Cout, Cin] weight, as the
+    inference route runs it; backward (_conv_backward) the statistics, tf_conv_dgrad_stride2_packed_f32 with ks = 1 (the even-even
+    pixels get dy . w, every other pixel +0) and tf_conv1x1_strided_wgrad_split_f32 (the rows x[n, 2 ho, 2 wo, :] read in place); torch
+    for a gradient whose kernel does not take the shape, counted in conv_train_counts."""
+
+    @staticmethod
+    def forward(ctx, x, w2d, terms):
+        with one_stream():
+            y = conv3x3(x, w2d, None, False, 2)
+        if y is None:
+            raise _NotApplicable()
+        ctx.terms = terms
+        ctx.save_for_backward(x, w2d)
+        return _own_tensor(y)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, w2d = ctx.saved_tensors
+        return _conv_backward(ctx.needs_input_grad, dy, x, w2d, 1, 2, ctx.terms) + (None,)
 
 
 def conv_train(x, w, stride):
@@ -2412,7 +2532,10 @@ def conv_train(x, w, stride):
     does not take the call (the input gradient under stride 2, Cout % 64 != 0, misaligned or over-size tensors) is computed by
     torch.ops.aten.convolution_backward inside the backward.  conv_train_counts() tells which path ran.
     w [Cout, Cin]: 1 x 1, stride 1, no padding: _LinearTrain on the [N H W, Cin] view of the activation (no bias, residual or ReLU), few
-    pixels under a long contraction cut into pieces as the inference route cuts them (_Conv1x1Train)."""
+    pixels under a long contraction cut into pieces as the inference route cuts them (_Conv1x1Train).
+    With set_strided_conv_training(True): the input gradient of the stride-2 3 x 3 is tf_conv_dgrad_stride2_packed_f32 (Cout % 64 == 0,
+    Cin % 4 == 0; else torch, counted), and w [Cout, Cin] with stride 2 (no padding) is taken too (_Conv1x1StridedTrain: forward
+    conv3x3(x, w, None, False, 2), own input and weight gradients, torch inside the backward where a gate fails, counted)."""
     if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and w.dim() == 2 and w.dtype == torch.float32
             and w.device == x.device):
         return None
@@ -2432,6 +2555,11 @@ def conv_train(x, w, stride):
             if y is not None and cin % 32:   # (linear() does not take K % 32 != 0: _LinearTrain's forward was F.linear, its backward ran)
                 _conv_train_counts["fwd_torch"] += 1
                 return y
+        elif w.shape[1] == cin and stride == 2 and strided_conv_training_enabled():
+            try:
+                y = _Conv1x1StridedTrain.apply(x, w, _terms())
+            except _NotApplicable:
+                y = None
     _conv_train_counts["fwd_own" if y is not None else "fwd_torch"] += 1
     return y
 
